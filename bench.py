@@ -7,8 +7,13 @@ FiniteDifferencesGrid N=100, Crank-Nicolson, fp64, batch=1024 independent seeded
 before the timed region starts) + one corbo_hip_solve of the whole resident batch (= batch x 10 SQP iterations) + the results
 (trajectories, chi2, status) copied into host-visible pinned memory ("to last result resident on host-visible memory").
 
-    python bench.py [--config 1|2|3|5] [--gpus N] [--steps K] [--warmup W] [--batch B] [--iterations I]
+    python bench.py [--config 1|2|3|5] [--gpus N] [--steps K] [--warmup W] [--batch B] [--iterations I] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds everything else, outside the timed
+region: the synchronous re-timing, counted iterations, the device-side gather, rooflines, the per-kernel split, host-inclusive
+timing, the secondary legs (config 3, 1 GPU) and the CPU baseline.  --dump-outputs DIR writes the last timed step's trajectories,
+chi2 and status as DIR/<name>.npy (float64; the inputs are seeded, so two builds can be compared output for output).
 
 --config selects another BASELINE.json configuration (parity-test cases; their lines are diagnostics, the driver's line is config 3):
   1  Van-der-Pol, FiniteDifferencesGrid N=20, batch 1           (configs[0]: plumbing; single-OCP latency through the boundary)
@@ -205,6 +210,25 @@ def counted_per_step(solver, solves):
         solver.solve(new_run=(i == 0))
         tot += int(solver.get_stats()["counted_iterations"])
     return tot
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(out_dir, solution, rank, world):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- trajectories [batch][nv], chi2 [batch], status [batch] --
+    as float64 .npy files (several ranks: one set per rank, <name>_rank<r>.npy).  Results beyond 64 MB in all are written as a fixed, seeded
+    sample of each rank's instances (rows in ascending order)."""
+    x, chi2, status = solution
+    per_instance = 8 * (x.shape[1] + 2)
+    budget = DUMP_BYTES_MAX // world
+    if x.shape[0] * per_instance > budget:
+        keep = np.sort(np.random.default_rng(20260928 + rank).choice(x.shape[0], budget // per_instance, replace=False))
+        x, chi2, status = x[keep], chi2[keep], status[keep]
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if world == 1 else f"_rank{rank}"
+    for name, a in (("trajectories", x), ("chi2", chi2), ("status", status)):
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def secondary_leg(cfg, iterations, device):
@@ -608,6 +632,9 @@ def main():
     ap.add_argument("--sync-steps", action="store_true", help="the host waits for every solve of the timed region (rounds 1-3) instead of enqueueing the steps back to back")
     ap.add_argument("--no-secondary", action="store_true", help="skip the legs over BASELINE configs 1, 2, 5 in the default (config 3, 1 GPU) line")
     ap.add_argument("--solve-only", action="store_true", help="profiling: only warm-up + timed steps (no roofline / host legs)")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline figure: the synchronous re-timing, counted iterations, the "
+                    "device-side gather, rooflines, per-kernel split, host-inclusive timing, the secondary legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's results (trajectories, chi2, status) as DIR/<name>.npy")
     args = ap.parse_args()
     cfg = args.config
     batch = args.batch if args.batch is not None else DEFAULT_BATCH[cfg]
@@ -707,9 +734,11 @@ def main():
         solver.fetch_solution()                   # (views of the pinned result buffers the last step's kernel filled)
     elapsed = time.perf_counter() - t0
     solve_ms_sum, n_solves = solver.get_timing(reset=True)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, solver.get_solution(), rank, world)
     # the same K steps with the host waiting for every solve (how rounds 1-3 timed the step): reported next to `value`, never in its place
     sync_ms_per_step = None
-    if pipelined:
+    if pipelined and args.full:
         fence()
         t1 = time.perf_counter()
         for _ in range(steps):
@@ -725,8 +754,6 @@ def main():
     red = sharding.reduce_stats(stats, float(chi2.sum()), int((status <= 1).sum()), dist, device=red_dev)  # SUM over ranks
     total_iters_per_step = red["lm_iterations"] * solves  # = world * batch * iterations * solves
     value = total_iters_per_step * steps / t_max
-    counted_step = sharding.reduce_stats({k: (counted_per_step(solver, solves) if k == "counted_iterations" else 0) for k in sharding.STAT_KEYS},
-                                         0.0, 0, dist, device=red_dev)["counted_iterations"]   # per step, all ranks (untimed extra step)
 
     line = {
         "metric": "SQP-iterations/sec over batch=1024 OCPs (nx=3,nu=2,N=100,fp64)",
@@ -751,13 +778,7 @@ def main():
                          "re-arm (D2D) + corbo_hip_solve + trajectories/chi2/status resident in pinned host memory ("
                          + ("written by the solve kernel as each instance finishes, corbo_hip_set_result_sink" if use_sink else "two D2H copies behind the solve")
                          + ", views from corbo_hip_fetch_solution); wall clock, barrier + synchronize on both sides, MAX over ranks"),
-        "synchronous_steps": ({"ms_per_step": sync_ms_per_step, "value": total_iters_per_step / (sync_ms_per_step * 1e-3),
-                               "what": "the same K steps with the host waiting for every solve before it re-arms the next one (corbo_hip_solve; the timed region of rounds 1-3)"}
-                              if sync_ms_per_step else None),
         "preheat": {"ms": args.preheat_ms, "untimed_steps": preheat_steps, "what": "untimed steps before the warm-up steps: steady-state clocks and warm pages (a cold process measures 0.74 - 0.77 ms per step over its first 25 steps, 0.68 ms afterwards)"},
-        "counted_iterations": int(counted_step),
-        "value_computed": (total_iters_per_step - counted_step) * steps / t_max,
-        "counted_note": "outer iterations after a converged step (|delta| <= eps2/2) are counted, not executed (corbo_hip_stats.counted_iterations); value_computed = executed iterations / s",
         "batch_steps_per_s": value / (B * world),
         "ms_per_step_ranks": [1e3 * t / steps for t in t_ranks],
         "solve_stats": {"passes_rank0": stats["passes"], "lm_iterations": int(red["lm_iterations"]),
@@ -765,6 +786,23 @@ def main():
                         "factorizations": int(red["factorizations"]), "counted_iterations": int(red["counted_iterations"]), "chi2_sum": red["chi2_sum"],
                         "ok_instances": int(red["ok_instances"])},
     }
+    if not args.full:   # a plain run: the headline figure only; everything below is --full
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    line["synchronous_steps"] = ({"ms_per_step": sync_ms_per_step, "value": total_iters_per_step / (sync_ms_per_step * 1e-3),
+                                  "what": "the same K steps with the host waiting for every solve before it re-arms the next one (corbo_hip_solve; the timed region of rounds 1-3)"}
+                                 if sync_ms_per_step else None)
+    counted_step = sharding.reduce_stats({k: (counted_per_step(solver, solves) if k == "counted_iterations" else 0) for k in sharding.STAT_KEYS},
+                                         0.0, 0, dist, device=red_dev)["counted_iterations"]   # per step, all ranks (untimed extra step)
+    line["counted_iterations"] = int(counted_step)
+    line["value_computed"] = (total_iters_per_step - counted_step) * steps / t_max
+    line["counted_note"] = ("outer iterations after a converged step (|delta| <= eps2/2) are counted, not executed (corbo_hip_stats.counted_iterations); "
+                            "value_computed = executed iterations / s")
     # ---- outside the timed region: the trajectories of ALL ranks collected straight from device memory (one RCCL all-gather on the
     #      handles' own HBM buffers, no host round trip) -- checked against the per-rank results that went through the host
     fence()

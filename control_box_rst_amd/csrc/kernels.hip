@@ -5794,10 +5794,18 @@ CORBO_HIP_BIG_ENTRIES(quadrotor)
 #ifdef CORBO_HIP_DYN_TU
 #define CORBO_HIP_CAT2(a, b) a##b
 #define CORBO_HIP_CAT(a, b) CORBO_HIP_CAT2(a, b)
+// -DCORBO_HIP_DYN_TU_PART=<k>: the model's entries split over three units that compile in parallel (the build does so for the small-block
+// family) -- 1: fused pass, 2: Hessian, 3: sweep, plant and the rest.  0 (default): every entry in this unit.
+#ifndef CORBO_HIP_DYN_TU_PART
+#define CORBO_HIP_DYN_TU_PART 0
+#endif
+#if CORBO_HIP_DYN_TU_PART == 0 || CORBO_HIP_DYN_TU_PART == 3
 bool CORBO_HIP_CAT(sweep_entry_, CORBO_HIP_DYN_TU_NAME)(int defect, const SweepParams& p, hipStream_t stream)
 {
     return launch_sweep_d<CORBO_HIP_DYN_TU>(defect, p, stream);   // (big-block family: shooting with its integrators, and the four collocation formulas)
 }
+#endif
+#if CORBO_HIP_DYN_TU_PART == 0 || CORBO_HIP_DYN_TU_PART == 1
 bool CORBO_HIP_CAT(pass_entry_, CORBO_HIP_DYN_TU_NAME)(int defect, const FactorParams& fp, const SweepParams& sp, hipStream_t stream)
 {
 #ifdef CORBO_HIP_DYN_TU_BIG   // no fused pass kernel for the big-block family
@@ -5807,11 +5815,17 @@ bool CORBO_HIP_CAT(pass_entry_, CORBO_HIP_DYN_TU_NAME)(int defect, const FactorP
     return launch_pass_d<CORBO_HIP_DYN_TU>(defect, fp, sp, stream);
 #endif
 }
+#endif
+#if CORBO_HIP_DYN_TU_PART == 0 || CORBO_HIP_DYN_TU_PART == 3
 void CORBO_HIP_CAT(plant_entry_, CORBO_HIP_DYN_TU_NAME)(const PlantParams& p, hipStream_t stream) { launch_plant_step_t<CORBO_HIP_DYN_TU>(p, stream); }
+#endif
+#if CORBO_HIP_DYN_TU_PART == 0 || CORBO_HIP_DYN_TU_PART == 2
 bool CORBO_HIP_CAT(hessian_entry_, CORBO_HIP_DYN_TU_NAME)(int defect, const SweepParams& p, const HessParams& hp, hipStream_t stream)
 {
     return launch_hessian_d<CORBO_HIP_DYN_TU>(defect, p, hp, stream);
 }
+#endif
+#if CORBO_HIP_DYN_TU_PART == 0 || CORBO_HIP_DYN_TU_PART == 3
 #ifdef CORBO_HIP_DYN_TU_BIG
 bool CORBO_HIP_CAT(stage_entry_, CORBO_HIP_DYN_TU_NAME)(const FactorParams& fp, const SweepParams& sp, int diag_only, double* jac_dump, hipStream_t stream)
 {
@@ -5925,6 +5939,7 @@ bool CORBO_HIP_CAT(factor_entry_, CORBO_HIP_DYN_TU_NAME)(const FactorParams& p, 
 bool CORBO_HIP_CAT(stage_entry_, CORBO_HIP_DYN_TU_NAME)(const FactorParams&, const SweepParams&, int, double*, hipStream_t) { return false; }
 bool CORBO_HIP_CAT(factor_entry_, CORBO_HIP_DYN_TU_NAME)(const FactorParams&, const SweepParams&, hipStream_t) { return false; }
 #endif
+#endif  // CORBO_HIP_DYN_TU_PART 0 / 3
 #endif  // CORBO_HIP_DYN_TU
 
 #ifndef CORBO_HIP_DYN_TU

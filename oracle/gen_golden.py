@@ -722,8 +722,64 @@ def tolerances():
         json.dump(ledger, f, indent=1)
 
 
+LIVE_BIG = ("vertex_init", "values_init", "jac_rows", "jac_cols", "jac_vals", "after_iter")
+LIVE_DROP = ("param_init", "param_lb", "param_ub", "H_diag_init", "rhs_init", "nnz_H")   # dump fields tests/test_oracle_vs_reference_live.py does not read
+
+
+def live():
+    """tests/golden/reference_live_dumps.npz: `ref_driver dump` of every random case of tests/test_oracle_vs_reference_live.py (what that
+    test compares the oracle with where the driver has not been built), keyed by seed, with the driver's arguments.  Inputs exact;
+    what the test compares bit for bit (structure, residual, Jacobian) as SHA-256 digests; the iterates in float32 with the exact
+    float64 rounding error and max |.| of each (the test adds the error to its deviation)."""
+    import scipy.sparse as sp
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_oracle_vs_reference_live as L
+    from conftest import desc_for
+    import oracle as O   # (oracle/oracle.py: this script's own directory comes first on sys.path)
+    O.load()
+    index, vinit, after = {}, [], []
+    n_vinit = n_after = 0
+    for seed in L.SEEDS:
+        args = L.case_args(seed)
+        d = json.loads(subprocess.check_output([DRIVER, "dump"] + args, timeout=120))
+        dims = O.OracleProblem(desc_for(d)).dims
+        nv = dims.nv
+        Jr = sp.coo_matrix((d["jac_vals"], (d["jac_rows"], d["jac_cols"])), shape=(dims.m, dims.n))
+        rec = {"args": args, "nv": nv, "header": {k: v for k, v in d.items() if k not in LIVE_BIG + LIVE_DROP},
+               "digests": L.exact_digests(d["jac_rows"], d["jac_cols"], d["values_init"], Jr), "vertex_init_at": n_vinit, "after_iter": []}
+        vinit.append(np.asarray(d["vertex_init"][:nv], np.float64))
+        n_vinit += nv
+        for a in d["after_iter"]:
+            v = np.asarray(a["vertex"][:nv], np.float64)
+            v32 = v.astype(np.float32)
+            assert np.all(np.isfinite(v32)), (seed, a["k"])
+            rec["after_iter"].append({"k": a["k"], "chi2": a["chi2"], "at": n_after,
+                                      "round_err": float(np.abs(v - v32.astype(np.float64)).max()), "absmax": float(np.abs(v).max())})
+            after.append(v32)
+            n_after += nv
+        index[str(seed)] = rec
+    np.savez_compressed(os.path.join(OUT, "reference_live_dumps.npz"), index=np.frombuffer(json.dumps(index, separators=(",", ":")).encode(), np.uint8),
+                        vertex_init=np.concatenate(vinit), after_vertex=np.concatenate(after))
+
+
+def describe():
+    """tests/golden/dropin_describe.json: the lines of `oracle/_ref/dropin_demo describe` (the adapter's recogniser on the reference's own
+    hypergraphs) and of its DROPIN_FUZZ runs, for tests/test_adapter_recogniser.py where the demo has not been built."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_adapter_recogniser as A
+    out = {"describe": A.run_demo(["describe"]), "fuzz": {}}
+    for seed in A.FUZZ_SEEDS:
+        out["fuzz"][str(seed)] = A.run_demo(A.FUZZ_ARGS, seed)
+    with open(os.path.join(OUT, "dropin_describe.json"), "w") as f:
+        json.dump(out, f, separators=(",", ":"))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
+    if len(sys.argv) > 1 and sys.argv[1] == "live":
+        return live()
+    if len(sys.argv) > 1 and sys.argv[1] == "describe":
+        return describe()
     if len(sys.argv) > 1 and sys.argv[1] == "tolerances":
         return tolerances()
     if len(sys.argv) > 1 and sys.argv[1] == "fuzzseed":

@@ -21,7 +21,7 @@ def _free_port():
 
 def _run(world, batch=64, steps=3, warmup=1):
     env = dict(os.environ, CORBO_BENCH_TEST_SHARED_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    args = ["bench.py", "--gpus", str(world), "--steps", str(steps), "--warmup", str(warmup), "--batch", str(batch), "--no-cpu-baseline"]
+    args = ["bench.py", "--full", "--gpus", str(world), "--steps", str(steps), "--warmup", str(warmup), "--batch", str(batch), "--no-cpu-baseline"]
     if world == 1:
         cmd = [sys.executable] + args
     else:

@@ -1,7 +1,12 @@
 """CPU test: the oracle against the genuine reference RUN HERE on random configurations (oracle/_ref/ref_driver, the binary that
 `make -C oracle ref` compiles from the reference's own sources; it travels with the repository snapshot, the sources do not).
-Skipped where the binary is absent.  Complements the committed golden vectors: dimensions and sparsity pattern, residual and
-Jacobian bit for bit (the oracle reproduces the reference's in-place finite-difference drift), iterates to the usual tolerance."""
+Where the binary is absent, the same cases come from its recorded dumps (tests/golden/reference_live_dumps.npz, written by
+`python oracle/gen_golden.py live`), checked against the arguments drawn here: the inputs exactly, what the test compares bit for bit
+as SHA-256 digests, the iterates in float32 with their exact rounding error (added to the deviation, so the tolerance is not
+widened).  Complements the committed golden vectors: dimensions and sparsity pattern, residual and Jacobian bit for bit (the oracle
+reproduces the reference's in-place finite-difference drift), iterates to the usual tolerance."""
+import functools
+import hashlib
 import json
 import os
 import subprocess
@@ -10,11 +15,12 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from conftest import ROOT, desc_for
+from conftest import GOLDEN, ROOT, desc_for
 from control_box_rst_amd import capi
 
 DRIVER = os.path.join(ROOT, "oracle", "_ref", "ref_driver")
-pytestmark = pytest.mark.skipif(not (os.path.exists(DRIVER) and os.access(DRIVER, os.X_OK)), reason="oracle/_ref/ref_driver not built")
+RECORDED = os.path.join(GOLDEN, "reference_live_dumps.npz")
+SEEDS = list(range(120)) + list(range(5000, 5060)) + list(range(6000, 6060))
 
 
 def _fmt(v):
@@ -82,25 +88,68 @@ def random_case(rng, zoo=0):
     return kv
 
 
-@pytest.mark.parametrize("seed", list(range(120)) + list(range(5000, 5060)) + list(range(6000, 6060)))
-def test_oracle_vs_live_reference(oracle_mod, seed):
+def case_args(seed):
+    """The driver's arguments of one random case."""
     rng = np.random.default_rng(424200 + seed)
     kv = random_case(rng, zoo=(2 if seed >= 6000 else 1 if seed >= 5000 else 0))   # 5000+: the reference's other benchmark systems (6000+: drawn after the linear models were added)
-    out = subprocess.check_output([DRIVER, "dump"] + [f"{k}={v}" for k, v in kv.items()], timeout=120)
-    g = json.loads(out)
+    return [f"{k}={v}" for k, v in kv.items()]
+
+
+def exact_digests(rows, cols, values, J):
+    """SHA-256 of what the test compares bit for bit: the sorted (row, col) list, the residual values and the summed CSR Jacobian
+    (-0.0 folded into 0.0, which the comparisons do not tell apart)."""
+    J = J.tocsr()
+    J.sum_duplicates()
+    J.sort_indices()
+    h = lambda *arrays: hashlib.sha256(b"".join(np.ascontiguousarray(a).tobytes() for a in arrays)).hexdigest()
+    return {"structure": h(np.array(sorted(zip(np.asarray(rows).tolist(), np.asarray(cols).tolist())), np.int64)),
+            "values": h(np.asarray(values, "<f8") + 0.0),
+            "jacobian": h(J.indptr.astype(np.int64), J.indices.astype(np.int64), np.asarray(J.data, "<f8") + 0.0)}
+
+
+@functools.lru_cache(maxsize=1)
+def _recorded():
+    with np.load(RECORDED) as z:
+        return json.loads(z["index"].tobytes()), z["vertex_init"], z["after_vertex"].astype(np.float64)
+
+
+def reference_dump(seed, args):
+    """`ref_driver dump` of a case: run here where the driver has been built, its recorded form otherwise."""
+    if os.path.exists(DRIVER) and os.access(DRIVER, os.X_OK):
+        return json.loads(subprocess.check_output([DRIVER, "dump"] + args, timeout=120))
+    index, vinit, after = _recorded()
+    rec = index[str(seed)]
+    assert rec["args"] == args, ("the recorded case was drawn with other arguments: python oracle/gen_golden.py live", seed)
+    nv, g = rec["nv"], dict(rec["header"])
+    g["vertex_init"] = vinit[rec["vertex_init_at"]: rec["vertex_init_at"] + nv]
+    g["digests"] = rec["digests"]
+    g["after_iter"] = [dict(a, vertex=after[a["at"]: a["at"] + nv]) for a in rec["after_iter"]]
+    return g
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_oracle_vs_live_reference(oracle_mod, seed):
+    args = case_args(seed)
+    kv = dict(a.split("=", 1) for a in args)   # (the assertion messages name the case)
+    g = reference_dump(seed, args)
     d = desc_for(g)
     p = oracle_mod.OracleProblem(d)
     for k in ("n", "lsq", "eq", "ineq", "bounds", "m", "nnz"):
         assert getattr(p.dims, k) == g[k], (kv, k)
     rows, cols = p.structure()
-    assert sorted(zip(rows.tolist(), cols.tolist())) == sorted(zip(g["jac_rows"], g["jac_cols"])), kv
     w = g["weights"]
     p.set_data(np.array(g["vertex_init"])[: p.dims.nv], xref=np.array(g["xf"]))
     values, jac = p.eval(*w)
-    assert np.array_equal(values, np.array(g["values_init"])), kv
     Jo = sp.coo_matrix((jac, (rows, cols)), shape=(p.dims.m, p.dims.n)).tocsr()
-    Jr = sp.coo_matrix((g["jac_vals"], (g["jac_rows"], g["jac_cols"])), shape=(p.dims.m, p.dims.n)).tocsr()
-    assert abs(Jo - Jr).max() == 0.0, kv
+    if "digests" in g:   # recorded case
+        got = exact_digests(rows, cols, values, Jo)
+        for k in ("structure", "values", "jacobian"):
+            assert got[k] == g["digests"][k], (kv, k)
+    else:
+        assert sorted(zip(rows.tolist(), cols.tolist())) == sorted(zip(g["jac_rows"], g["jac_cols"])), kv
+        assert np.array_equal(values, np.array(g["values_init"])), kv
+        Jr = sp.coo_matrix((g["jac_vals"], (g["jac_rows"], g["jac_cols"])), shape=(p.dims.m, p.dims.n)).tocsr()
+        assert abs(Jo - Jr).max() == 0.0, kv
     for a in g["after_iter"]:
         q = oracle_mod.OracleProblem(d)
         q.set_data(q.init_trajectory(g["x0"], g["xf"]), xref=np.array(g["xf"]))
@@ -109,6 +158,8 @@ def test_oracle_vs_live_reference(oracle_mod, seed):
             status, chi2, _ = q.solve(opts, new_run=(s == 0))
         ref = np.array(a["vertex"])[: q.dims.nv]
         # random, sometimes poorly conditioned cases: the finite-difference noise (1e-7 relative in J) is amplified a little more
-        # than on the fixtures; values and Jacobian above are exact
-        assert np.abs(q.x() - ref).max() <= 2e-5 * max(1.0, np.abs(ref).max()), (kv, a["k"], np.abs(q.x() - ref).max())
+        # than on the fixtures; values and Jacobian above are exact.  (Recorded cases: ref is the float32 iterate, round_err its exact
+        # distance from the float64 one and absmax the float64 iterate's max |.|: deviation + round_err bounds the deviation from it.)
+        dev = np.abs(q.x() - ref).max() + a.get("round_err", 0.0)
+        assert dev <= 2e-5 * max(1.0, a.get("absmax", np.abs(ref).max())), (kv, a["k"], dev)
         assert abs(chi2 - a["chi2"]) <= 5e-6 * max(1.0, abs(a["chi2"])), (kv, a["k"])

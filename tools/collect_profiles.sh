@@ -12,9 +12,9 @@ cd /tmp && export TMPDIR=/tmp
 run() { name=$1; shift; timeout 900 rocprofv3 "$@" > "$OUT/$name.log" 2>&1 || echo "rocprofv3 $name failed ($?)"; }
 first() { find "$OUT/$1" -name "$2" | head -1; }
 # ---- kernel traces
-run bench  --kernel-trace --stats -d "$OUT/bench" -o bench --output-format csv -- python "$ROOT/bench.py" --no-cpu-baseline --no-secondary
+run bench  --kernel-trace --stats -d "$OUT/bench" -o bench --output-format csv -- python "$ROOT/bench.py" --full --no-cpu-baseline --no-secondary
 run sweep  --kernel-trace --stats -d "$OUT/sweep" -o sweep --output-format csv -- python "$ROOT/tools/profile_sweep.py" 1024 50
-run cfg5   --kernel-trace --stats -d "$OUT/cfg5" -o cfg5 --output-format csv -- python "$ROOT/bench.py" --config 5 --no-cpu-baseline
+run cfg5   --kernel-trace --stats -d "$OUT/cfg5" -o cfg5 --output-format csv -- python "$ROOT/bench.py" --full --config 5 --no-cpu-baseline
 run cfg5ns --kernel-trace --stats -d "$OUT/cfg5ns" -o cfg5ns --output-format csv -- python "$ROOT/tools/profile_cfg5.py" 512 3 0 nospec
 run loop   --kernel-trace --stats -d "$OUT/loop" -o loop --output-format csv -- python "$ROOT/tools/mpc_loop.py" 1024 100 10 call
 run band   --kernel-trace --stats -d "$OUT/band" -o band --output-format csv -- python "$ROOT/tools/band_time.py"
@@ -25,11 +25,11 @@ BATCH=8192 run b8192  --kernel-trace --stats -d "$OUT/b8192" -o b8192 --output-f
 # ---- HBM traffic counters (separate passes): the stand-alone sweep, and the run-to-completion solve kernel
 run sfetch --pmc FETCH_SIZE -d "$OUT/sfetch" -o q --output-format csv -- python "$ROOT/tools/profile_sweep.py" 1024 10
 run swrite --pmc WRITE_SIZE -d "$OUT/swrite" -o q --output-format csv -- python "$ROOT/tools/profile_sweep.py" 1024 10
-run lfetch --pmc FETCH_SIZE -d "$OUT/lfetch" -o q --output-format csv -- python "$ROOT/bench.py" --solve-only --steps 10 --warmup 2
-run lwrite --pmc WRITE_SIZE -d "$OUT/lwrite" -o q --output-format csv -- python "$ROOT/bench.py" --solve-only --steps 10 --warmup 2
+run lfetch --pmc FETCH_SIZE -d "$OUT/lfetch" -o q --output-format csv -- python "$ROOT/bench.py" --full --solve-only --steps 10 --warmup 2
+run lwrite --pmc WRITE_SIZE -d "$OUT/lwrite" -o q --output-format csv -- python "$ROOT/bench.py" --full --solve-only --steps 10 --warmup 2
 # ---- issue / wait counters of the solve kernel, fp64 matrix-core counters of the cfg-5 kernels
-run sq1 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES -d "$OUT/sq1" -o q --output-format csv -- python "$ROOT/bench.py" --solve-only --steps 5 --warmup 1
-run sq2 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_WAIT_INST_LDS SQ_WAVE_CYCLES -d "$OUT/sq2" -o q --output-format csv -- python "$ROOT/bench.py" --solve-only --steps 5 --warmup 1
+run sq1 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES -d "$OUT/sq1" -o q --output-format csv -- python "$ROOT/bench.py" --full --solve-only --steps 5 --warmup 1
+run sq2 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_WAIT_INST_LDS SQ_WAVE_CYCLES -d "$OUT/sq2" -o q --output-format csv -- python "$ROOT/bench.py" --full --solve-only --steps 5 --warmup 1
 run hess   --kernel-trace --stats -d "$OUT/hess" -o hess --output-format csv -- python "$ROOT/tools/hessian_split_ab.py" 1024 0
 run hess1  --kernel-trace --stats -d "$OUT/hess1" -o hess1 --output-format csv -- python "$ROOT/tools/hessian_split_ab.py" 1 2
 run mfma --pmc SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU -d "$OUT/mfma" -o q --output-format csv -- python "$ROOT/tools/profile_cfg5.py" 512 3
@@ -39,8 +39,8 @@ cd "$ROOT"
 P=$ROOT/profiles
 for n in bench sweep cfg5 cfg5ns loop band freedt xe long b8192 hess hess1; do s=$(first $n "*kernel_stats.csv"); [ -n "$s" ] && cp "$s" "$P/${RND}_${n}_kernel_stats.csv"; done; [ -f "$P/${RND}_hess_kernel_stats.csv" ] && mv "$P/${RND}_hess_kernel_stats.csv" "$P/${RND}_hessian_kernel_stats.csv"; [ -f "$P/${RND}_hess1_kernel_stats.csv" ] && mv "$P/${RND}_hess1_kernel_stats.csv" "$P/${RND}_hessian_single_kernel_stats.csv"; [ -f "$P/${RND}_cfg5ns_kernel_stats.csv" ] && mv "$P/${RND}_cfg5ns_kernel_stats.csv" "$P/${RND}_cfg5_nospec_kernel_stats.csv"
 python tools/summarize_pmc.py sweep "$(first sfetch '*counter_collection.csv')" "$(first swrite '*counter_collection.csv')" 1024 100 "$TAG, tools/profile_sweep.py 1024 10" | cut -c1-300
-python tools/summarize_pmc.py solve "$(first lfetch '*counter_collection.csv')" "$(first lwrite '*counter_collection.csv')" 1024 100 "$TAG, bench.py --solve-only --steps 10 --warmup 2" | cut -c1-300
-python tools/summarize_pmc.py sq "$(first sq1 '*counter_collection.csv')" "$(first sq2 '*counter_collection.csv')" 1024 100 "$TAG, bench.py --solve-only --steps 5 --warmup 1" | cut -c1-600
+python tools/summarize_pmc.py solve "$(first lfetch '*counter_collection.csv')" "$(first lwrite '*counter_collection.csv')" 1024 100 "$TAG, bench.py --full --solve-only --steps 10 --warmup 2" | cut -c1-300
+python tools/summarize_pmc.py sq "$(first sq1 '*counter_collection.csv')" "$(first sq2 '*counter_collection.csv')" 1024 100 "$TAG, bench.py --full --solve-only --steps 5 --warmup 1" | cut -c1-600
 python tools/summarize_pmc.py cfg5 "$(first qfetch '*counter_collection.csv')" "$(first qwrite '*counter_collection.csv')" 512 200 "$TAG, tools/profile_cfg5.py 512 3" | cut -c1-900
 python tools/summarize_pmc.py mfma "$(first mfma '*counter_collection.csv')" 512 200 "$TAG, tools/profile_cfg5.py 512 3" | cut -c1-900
 cp "$(first sfetch '*counter_collection.csv')" "$P/${RND}_sweep_pmc_fetch_counter_collection.csv"; cp "$(first swrite '*counter_collection.csv')" "$P/${RND}_sweep_pmc_write_counter_collection.csv"
@@ -53,10 +53,10 @@ cd "$ROOT"
 { python tools/xe_time.py; python tools/xe_batch_sweep.py; python tools/narrow_band_phases.py; } 2>&1 | grep -v amdgpu.ids > "$P/${RND}_extra_edge_routes.txt"
 { python tools/bt_phases.py 0 1; python tools/bt_phases.py 900 1024; } 2>&1 | grep -v amdgpu.ids | cut -c1-400 > "$P/${RND}_xe_pass_phases.txt"
 # ---- the bench lines of the same build on the same box (the profile-derived fields now resolve against the files above)
-python bench.py > "$P/${RND}_bench_line.json" 2> "$OUT/benchline3.err"
-python bench.py --config 5 > "$P/${RND}_bench_line_cfg5.json" 2> "$OUT/benchline5.err"
-python bench.py --config 2 > "$P/${RND}_bench_line_cfg2.json" 2> "$OUT/benchline2.err"
-python bench.py --config 1 > "$P/${RND}_bench_line_cfg1.json" 2> "$OUT/benchline1.err"
+python bench.py --full > "$P/${RND}_bench_line.json" 2> "$OUT/benchline3.err"
+python bench.py --full --config 5 > "$P/${RND}_bench_line_cfg5.json" 2> "$OUT/benchline5.err"
+python bench.py --full --config 2 > "$P/${RND}_bench_line_cfg2.json" 2> "$OUT/benchline2.err"
+python bench.py --full --config 1 > "$P/${RND}_bench_line_cfg1.json" 2> "$OUT/benchline1.err"
 mkdir -p "$OUT/profiles"; cp "$P"/${RND}_* "$P"/sweep_pmc_latest.json "$OUT/profiles/"
 head -3 "$P/${RND}_bench_kernel_stats.csv" | cut -c1-200; head -3 "$P/${RND}_sweep_kernel_stats.csv" | cut -c1-200; head -5 "$P/${RND}_cfg5_kernel_stats.csv" | cut -c1-200
 for c in "" _cfg5 _cfg2 _cfg1; do python -c "

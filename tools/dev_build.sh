@@ -9,7 +9,7 @@ FLAGS="--offload-arch=gfx950 --offload-compress -O3 -std=c++17 -fPIC -Wno-unused
 /opt/rocm/bin/hipcc $FLAGS -DCORBO_HIP_DEV_FAST -DCORBO_HIP_DYN_TU=CORBO_HIP_DYN_UNICYCLE -DCORBO_HIP_DYN_TU_NAME=unicycle "$@" \
     -c kernels.hip -o /tmp/kernels_unicycle_$name.o -Rpass-analysis=kernel-resource-usage 2> /tmp/$name.remarks || { tail -30 /tmp/$name.remarks; exit 1; }
 grep -A9 "lm_pass_kernelILi2ELi3ELb0ELb1ELi101" /tmp/$name.remarks | grep -E "VGPRs|Scratch|SGPRs" | sed 's/.*remark: //' | tr '\n' ' '; echo
-objs=$(ls _obj/*.o | grep -v kernels_unicycle.o)
+objs=$(ls _obj/*.o | grep -v "_obj/kernels_unicycle\(_p[123]\)\?\.o")   # (whole unit or the three part units of build())
 if [ -n "$MAIN" ]; then   # MAIN=1: also the main unit (model-independent kernels: factor / big-block family / helpers) with the extra flags
     /opt/rocm/bin/hipcc $FLAGS "$@" -c kernels.hip -o /tmp/kernels_main_$name.o
     /opt/rocm/bin/hipcc $FLAGS -DCORBO_HIP_DYN_TU=CORBO_HIP_DYN_QUADROTOR -DCORBO_HIP_DYN_TU_NAME=quadrotor -DCORBO_HIP_DYN_TU_BIG "$@" -c kernels.hip -o /tmp/kernels_quad_$name.o

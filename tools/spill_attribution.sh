@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 for lib in ship nospill; do
   if [ $lib = nospill ]; then export CORBO_HIP_LIB=$ROOT/control_box_rst_amd/csrc/libcorbo_hip_nospill.so; else unset CORBO_HIP_LIB; fi
   for c in WRITE_SIZE FETCH_SIZE; do
-    timeout 600 rocprofv3 --pmc $c -d "$OUT/${lib}_$c" -o q --output-format csv -- python "$ROOT/bench.py" --solve-only --steps 10 --warmup 2 --no-secondary > "$OUT/${lib}_$c.log" 2>&1
+    timeout 600 rocprofv3 --pmc $c -d "$OUT/${lib}_$c" -o q --output-format csv -- python "$ROOT/bench.py" --full --solve-only --steps 10 --warmup 2 --no-secondary > "$OUT/${lib}_$c.log" 2>&1
   done
 done
 python - <<PY
