@@ -52,6 +52,15 @@ class ProblemDesc(C.Structure):
     ]
 
 
+class WeightFactors(C.Structure):
+    """corbo_hip_weight_factors: non-diagonal weights beside the descriptor (corbo_hip_create_weighted).  mask bit 0 Q, bit 1 R, bit 2 Qf; each factor
+    the upper Cholesky factor U (W = U^T U), row-major [i * nx + j] (R: [i * nu + j])."""
+    _fields_ = [
+        ("mask", C.c_int32), ("reserved0", C.c_int32),
+        ("q_sqrt", C.c_double * (MAX_NX * MAX_NX)), ("r_sqrt", C.c_double * (MAX_NU * MAX_NU)), ("qf_sqrt", C.c_double * (MAX_NX * MAX_NX)),
+    ]
+
+
 class Dims(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("nv", "n", "lsq", "eq", "ineq", "bounds", "m", "nnz")]
 
@@ -106,7 +115,7 @@ EXPORTED_SYMBOLS = (
     "corbo_hip_closed_loop", "corbo_hip_fetch_solution", "corbo_hip_get_timing", "corbo_hip_time_sweep_each", "corbo_hip_set_result_sink", "corbo_hip_eval_dynamics", "corbo_hip_set_option", "corbo_hip_prepare_slots", "corbo_hip_get_dt", "corbo_hip_resample_into",
     "corbo_hip_device_count", "corbo_hip_shard_bounds", "corbo_hip_device_row_stride",
     "corbo_hip_set_references", "corbo_hip_set_reference_trajectory", "corbo_hip_hessian_nnz", "corbo_hip_hessian_structure", "corbo_hip_eval_hessians", "corbo_hip_eval_hessians_views", "corbo_hip_linear_form_structure", "corbo_hip_eval_linear_form", "corbo_hip_eval_objective_gradient",
-    "corbo_hip_sizeof", "corbo_hip_set_previous_control", "corbo_hip_get_phase_cycles", "corbo_hip_create_routed", "corbo_hip_factor_route", "corbo_hip_stage_function_kind", "corbo_hip_eval_stage_function",
+    "corbo_hip_sizeof", "corbo_hip_set_previous_control", "corbo_hip_get_phase_cycles", "corbo_hip_create_routed", "corbo_hip_create_weighted", "corbo_hip_factor_route", "corbo_hip_stage_function_kind", "corbo_hip_eval_stage_function",
 )
 
 
@@ -131,7 +140,8 @@ def load() -> C.CDLL:
         pass
     lib = C.CDLL(_LIB_PATH)
     lib.corbo_hip_sizeof.argtypes, lib.corbo_hip_sizeof.restype = [C.c_int], C.c_size_t
-    for which, mirror in ((0, ProblemDesc), (1, Dims), (2, LmOpts), (3, Stats)):
+    mirrors = ((0, ProblemDesc), (1, Dims), (2, LmOpts), (3, Stats)) + (((4, WeightFactors),) if hasattr(lib, "corbo_hip_create_weighted") else ())
+    for which, mirror in mirrors:   # (an older build loaded through CORBO_HIP_LIB has no corbo_hip_weight_factors)
         if lib.corbo_hip_sizeof(which) != C.sizeof(mirror):
             raise RuntimeError(f"{_LIB_PATH} was built from another include/corbo_hip.h: sizeof({mirror.__name__}) = {C.sizeof(mirror)} here, "
                                f"{lib.corbo_hip_sizeof(which)} in the library -- rebuild it (python -c 'import __graft_entry__ as g; g.build()')")
@@ -146,6 +156,8 @@ def load() -> C.CDLL:
     lib.corbo_hip_stage_function_kind.argtypes = [C.c_int]
     lib.corbo_hip_eval_stage_function.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, dp]
     lib.corbo_hip_create_routed.argtypes = [C.POINTER(ProblemDesc), C.c_int, C.c_int, C.c_uint32, C.POINTER(H)]
+    if hasattr(lib, "corbo_hip_create_weighted"):
+        lib.corbo_hip_create_weighted.argtypes = [C.POINTER(ProblemDesc), C.POINTER(WeightFactors), C.c_int, C.c_int, C.c_uint32, C.POINTER(H)]
     lib.corbo_hip_factor_route.argtypes = [H]
     lib.corbo_hip_factor_route.restype = C.c_int
     lib.corbo_hip_destroy.argtypes = [H]

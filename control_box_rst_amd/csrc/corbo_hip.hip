@@ -364,7 +364,8 @@ try {
 }
 ABI_CATCH
 
-static int create_impl(const corbo_hip_problem_desc* desc, int batch, int device, uint32_t route, corbo_hip_handle* out);
+static int create_impl(const corbo_hip_problem_desc* desc, int batch, int device, uint32_t route, corbo_hip_handle* out,
+                       const corbo_hip_weight_factors* wf = nullptr);
 
 int corbo_hip_create(const corbo_hip_problem_desc* desc, int batch, int device, corbo_hip_handle* out)
 try {
@@ -382,12 +383,21 @@ try {
 }
 ABI_CATCH
 
-static int create_impl(const corbo_hip_problem_desc* desc, int batch, int device, uint32_t route, corbo_hip_handle* out)
+int corbo_hip_create_weighted(const corbo_hip_problem_desc* desc, const corbo_hip_weight_factors* weights, int batch, int device, uint32_t route,
+                              corbo_hip_handle* out)
+try {
+    if (!desc || !out || batch < 1) return fail(CORBO_HIP_ERR_INVALID, "null argument or batch < 1");
+    *out = nullptr;
+    return create_impl(desc, batch, device, route, out, weights);
+}
+ABI_CATCH
+
+static int create_impl(const corbo_hip_problem_desc* desc, int batch, int device, uint32_t route, corbo_hip_handle* out, const corbo_hip_weight_factors* wf)
 {
     // owns the half-built handle until it is handed to the caller (exceptions and early returns free everything created so far)
     struct Owner { corbo_hip_solver* p; ~Owner() { if (p) corbo_hip_destroy(p); } } owner{new corbo_hip_solver()};
     corbo_hip_solver* h = owner.p;
-    std::string err = build_structure(*desc, h->S);
+    std::string err = wf ? build_structure_weighted(*desc, *wf, h->S) : build_structure(*desc, h->S);
     if (!err.empty()) return fail(CORBO_HIP_ERR_INVALID, err);
     const Structure& S = h->S;
     {   // device kernels exist for this descriptor?
@@ -495,7 +505,11 @@ static int create_impl(const corbo_hip_problem_desc* desc, int batch, int device
         CREATE_TRY(hipMalloc((void**)&h->d_lin, ab.size() * sizeof(double)));
         CREATE_TRY(hipMemcpy(h->d_lin, ab.data(), ab.size() * sizeof(double), hipMemcpyHostToDevice));
     }
-    if (S.desc.weights_dense) {
+    if (S.desc.weights_dense && !S.wside.empty()) {   // big-block family (corbo_hip_create_weighted): blocks of wdense_stride(nx) = nx * nx doubles
+        CREATE_TRY(hipMalloc((void**)&h->d_wdense, S.wside.size() * sizeof(double)));
+        CREATE_TRY(hipMemcpy(h->d_wdense, S.wside.data(), S.wside.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    else if (S.desc.weights_dense) {
         double wd[48];
         std::memcpy(wd, S.desc.q_sqrt, 16 * sizeof(double)); std::memcpy(wd + 16, S.desc.r_sqrt, 16 * sizeof(double)); std::memcpy(wd + 32, S.desc.qf_sqrt, 16 * sizeof(double));
         CREATE_TRY(hipMalloc((void**)&h->d_wdense, sizeof(wd)));
@@ -535,7 +549,7 @@ static int create_impl(const corbo_hip_problem_desc* desc, int batch, int device
             CREATE_TRY(hipMemset(h->d_xe0, 0, 2 * BT * (size_t)S.N * S.nx * sizeof(double)));
         }
         if (big_family_dims(S.nx, S.nu) && !band_route_early) {
-            h->stage_cache_stride = big_stage_cache_doubles(*desc, S.N);
+            h->stage_cache_stride = big_stage_cache_doubles(S.desc, S.N);   // (S.desc: weights_dense of a weighted handle -- its dense cost blocks are cached too)
             const size_t bytes = BT * h->stage_cache_stride * sizeof(double);
             if (bytes > ((size_t)2 << 30)) h->stage_cache_stride = 0;   // (beyond 2 GB the first factorisation integrates twice, as before)
             else CREATE_TRY(hipMalloc((void**)&h->d_stage_cache, bytes));
@@ -807,8 +821,17 @@ try {
 }
 ABI_CATCH
 
+// non-diagonal weights around a big-block model: the DENSE sweep exists residual-only (the Jacobian of these handles is the stage kernel's) --
+// a launch that asks the sweep for a Jacobian has no kernel (launch_sweep_t launches nothing for it)
+static bool wd_big_needs_sweep_jacobian(corbo_hip_handle h, const SweepParams& p)
+{
+    return !h->S.wside.empty() && !(p.mode == 0 || (p.skip_jac && p.mode >= 2));
+}
+
 static int launch_sweep_checked(corbo_hip_handle h, const SweepParams& p)
 {
+    if (wd_big_needs_sweep_jacobian(h, p))
+        return fail(CORBO_HIP_ERR_UNSUPPORTED, "non-diagonal weights around a big-block model: no sweep kernel with a Jacobian (the stage kernel differentiates these handles)");
     if (!launch_sweep(h->S.desc, p, h->stream)) return fail(CORBO_HIP_ERR_UNSUPPORTED, "no sweep kernel for this dynamics/defect");
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1031,7 +1054,7 @@ static int solve_impl(corbo_hip_handle h, const corbo_hip_lm_opts* o, int new_ru
                 HIP_TRY(hipGetLastError());
                 stamp();
             }
-            if (!launch_sweep(h->S.desc, sp, st_of[i])) return fail(CORBO_HIP_ERR_UNSUPPORTED, "no sweep kernel for this dynamics/defect");
+            if (wd_big_needs_sweep_jacobian(h, sp) || !launch_sweep(h->S.desc, sp, st_of[i])) return fail(CORBO_HIP_ERR_UNSUPPORTED, "no sweep kernel for this dynamics/defect");
             HIP_TRY(hipGetLastError());
             if (spec) {   // after the prologue: every slot free; after a pass: candidates merged, the next ones started
                 launch_big_spec(spec_params(mode == 3 ? 0 : 1, counter), st_of[i]);
@@ -1796,7 +1819,11 @@ try {
     const bool high_big = big_family_dims(h->S.nx, h->S.nu) && h->S.desc.shooting_integrator >= 5;
     if (jac_out && high_big && (h->band.n != 0 || h->S.desc.final_eq_mask))
         return fail(CORBO_HIP_ERR_UNSUPPORTED, "corbo_hip_eval with a Jacobian: Runge-Kutta 5 - 7 around a big-block model with a partial terminal equality");
-    const SweepParams spe = h->sweep_params((jac_out && !high_big) ? 1 : 0, 0, w_eq, w_ineq, w_bounds, nullptr);
+    // (non-diagonal weights around a big-block model: the residual-only sweep with the dense cost rows; the Jacobian is the stage kernel's)
+    const bool wd_big = !h->S.wside.empty();
+    if (jac_out && wd_big && h->S.desc.final_eq_mask)
+        return fail(CORBO_HIP_ERR_UNSUPPORTED, "corbo_hip_eval with a Jacobian: non-diagonal weights around a big-block model with a partial terminal equality");
+    const SweepParams spe = h->sweep_params((jac_out && !high_big && !wd_big) ? 1 : 0, 0, w_eq, w_ineq, w_bounds, nullptr);
     int rc = launch_sweep_checked(h, spe);
     if (rc) return rc;
     // (a partial terminal equality: the stage kernel's dump writes the full constraint's block -- kernels.hip, big_stage_edges --, the sweep kernel's Jacobian is returned)
@@ -1875,6 +1902,8 @@ static int hessian_common(corbo_hip_handle h, const HessianStructure*& Hout, boo
 {
     if (!h->have_data) return fail(CORBO_HIP_ERR_STATE, "corbo_hip_set_instance_data must be called first");
     if (h->S.has_extra()) return fail(CORBO_HIP_ERR_UNSUPPORTED, "Hessian-path operators with integral-form constraints / a control-deviation term: not built");
+    // (their kernels read the descriptor-path table of 16 doubles per factor: never the diagonal, never a misread 12 x 12 factor)
+    if (!h->S.wside.empty()) return fail(CORBO_HIP_ERR_UNSUPPORTED, "Hessian-path operators with non-diagonal weights around a big-block model (corbo_hip_create_weighted): not built");
     auto& c = h->hess_cache[lower ? 1 : 0];
     if (!c.valid) {   // once per (handle, lower): the walk over the edges and its two device tables
         build_hessian_structure(h->S, lower, c.H);
@@ -2302,6 +2331,7 @@ size_t corbo_hip_sizeof(int which)
         case 1: return sizeof(corbo_hip_dims);
         case 2: return sizeof(corbo_hip_lm_opts);
         case 3: return sizeof(corbo_hip_stats);
+        case 4: return sizeof(corbo_hip_weight_factors);
         default: return 0;
     }
 }

@@ -14,6 +14,7 @@
 //
 // Both are table driven (structure.hpp); nothing here knows about edge objects.
 #include "kernels.hpp"
+#include <type_traits>
 
 namespace corbo_hip {
 
@@ -380,6 +381,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams& p, const int mode,
         else __builtin_nontemporal_store(val, &vout[row]);
     };
     constexpr int DM = (NX > NU) ? NX : NU;
+    constexpr int WDS = wdense_stride(NX);   // doubles per factor block of the weight table (16; big-block family: NX * NX)
     const int wdm = (DENSE && p.mp.wdense) ? p.mp.wdense_mask : 0;   // non-diagonal weights: bit 0 Q, bit 1 R, bit 2 Qf (uniform; 0 for every diagonal problem)
     // differences x_j - ref_j of the whole vertex that component v (index c, class cls: 0 state, 1 control, 2 final state) belongs to
     auto vertex_diffs = [&](int v, int c, int dim, int cls, double (&xd)[DM]) {
@@ -433,7 +435,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams& p, const int mode,
         if (DENSE && wdm && cls < 3 && ((wdm >> cls) & 1)) {
             // dense weight: column c of the (upper-triangular) block U, every row by central differences of the edge's own value
             if (!ci.fixed && ci.cost_joff >= 0) {
-                const double* U = p.mp.wdense + 16 * cls;
+                const double* U = p.mp.wdense + WDS * cls;
                 double xd[DM];
                 vertex_diffs(v, c, dim, cls, xd);
                 double refc = 0.0;   // the component's own reference (the perturbed difference is (x_c +- delta) - ref_c)
@@ -491,7 +493,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams& p, const int mode,
                 if (cls < 3 && ((wdm >> cls) & 1)) {
                     double xd[DM];
                     vertex_diffs(v, c, dim, cls, xd);
-                    val = dense_weight_row<DM>(p.mp.wdense + 16 * cls, c, dim, xd, ((ci.cost_row - c) & 1) != 0);   // (the edge's first row)
+                    val = dense_weight_row<DM>(p.mp.wdense + WDS * cls, c, dim, xd, ((ci.cost_row - c) & 1) != 0);   // (the edge's first row)
                 }
             }
             put_value(ci.cost_row, val);
@@ -2714,6 +2716,10 @@ constexpr int big_lds_total(int nx, int nu)
     return 2 * half + ((s * s + 2 * s + nu * nu + 2 * nu * nx + 2 * nu + 1) & ~1);
 }
 
+// non-diagonal weights (WD instantiations): per interval the dense cost blocks behind BigLds::TOTAL -- Q (x_k; the last block: Qf) [NX][NX] and R [NU][NU],
+// column c = the central differences of U (x - ref) in component c (big_stage_edges); cached with the halves by the first factorisation
+constexpr int big_wd_doubles(int nx, int nu) { return (nx * nx + nu * nu + 1) & ~1; }
+
 template <int NX, int NU>
 struct BigLds {
     // LDS of the stage kernel.  The x_{k+1} block C of the local defect Jacobian [A | B | C] is DIAGONAL (only e_i depends on
@@ -2854,8 +2860,9 @@ __global__ __launch_bounds__(64) void big_first_kernel(const FactorParams p)
 // ---- per (stage, instance): everything of the factorisation that does not depend on the neighbouring stages.  The local Jacobian
 //      G = [A | B | C], the defect residual and the single-entry rows of the stage's components are in the LDS context c (written by
 //      the stage kernel straight from the finite differences: the Jacobian of this family never exists in HBM).
-template <int NX, int NU, bool USE_MFMA, bool DENSEC = false, bool ARROW = false>
-__device__ __forceinline__ void big_assemble_stage(const BigCtx<NX, NU>& c, const int N, const int k, const int lane, double* wk, const double mu_eff)
+template <int NX, int NU, bool USE_MFMA, bool DENSEC = false, bool ARROW = false, bool WD = false>
+__device__ __forceinline__ void big_assemble_stage(const BigCtx<NX, NU>& c, const int N, const int k, const int lane, double* wk, const double mu_eff,
+                                                   const double* wq = nullptr, const int wdm = 0)
 {
     using BL = BigLds<NX, NU>;
     constexpr int S = NX + NU;
@@ -2912,6 +2919,21 @@ __device__ __forceinline__ void big_assemble_stage(const BigCtx<NX, NU>& c, cons
             for (int a = 0; a < NU; ++a)
 #pragma unroll
                 for (int b = 0; b < NU; ++b) H[a][b] = Mm[(NX + a) * S + NX + b] + ((a == b) ? dg[NX + a] + mu_eff : 0.0);
+            if constexpr (WD) {   // dense R: the off-diagonal entries of its Gram matrix C^T C (the diagonal and the gradient are in dg / gd)
+                if ((wdm >> 1) & 1) {
+                    const double* wr = wq + NX * NX;
+#pragma unroll
+                    for (int a = 0; a < NU; ++a)
+#pragma unroll
+                        for (int b = 0; b < NU; ++b) {
+                            if (a == b) continue;
+                            double g = 0.0;
+#pragma unroll
+                            for (int r = 0; r < NU; ++r) g += wr[r * NU + a] * wr[r * NU + b];
+                            H[a][b] += g;
+                        }
+                }
+            }
             chol_inv<NU>(H);
 #pragma unroll
             for (int a = 0; a < NU; ++a)
@@ -2973,6 +2995,14 @@ __device__ __forceinline__ void big_assemble_stage(const BigCtx<NX, NU>& c, cons
             }
         }
         if (i == j) d += dg[i] + mu_eff;
+        if constexpr (WD) {   // dense Q (the last block: Qf): the off-diagonal entries of C^T C
+            if (i != j && ((wdm >> (stage ? 0 : 2)) & 1)) {
+                double g = 0.0;
+#pragma unroll
+                for (int r = 0; r < NX; ++r) g += wq[r * NX + i] * wq[r * NX + j];
+                d += g;
+            }
+        }
         wk[BL::WS_L + e] = d; wk[BL::WS_Y + e] = cx; wk[BL::WS_DN + e] = dn;
     }
     if (lane < NX) {
@@ -3034,9 +3064,10 @@ __device__ __forceinline__ void big_assemble_stage(const BigCtx<NX, NU>& c, cons
 #pragma clang fp contract(off)
 // USERINEQ: the stage inequality is a user state function (csrc/stage_functions/) -- an instantiation of its own, so that the keep-out ball's kernels (cfg 5)
 // are what they were: its three-component copies, no branch (an out-of-line helper behind a uniform branch cost cfg 5 8.05 -> 8.41 ms per solve: 192 bytes of scratch per lane)
-template <int DYN, int DEFECT = CORBO_HIP_DEFECT_RK4_SHOOTING, bool ARROW = false, bool USERINEQ = false>
+// WD: non-diagonal weights (corbo_hip_create_weighted): wq = the interval's dense cost blocks (big_wd_doubles)
+template <int DYN, int DEFECT = CORBO_HIP_DEFECT_RK4_SHOOTING, bool ARROW = false, bool USERINEQ = false, bool WD = false>
 __device__ __forceinline__ void big_stage_edges(const FactorParams& p, const SweepParams& sp, const BigCtx<Dynamics<DYN>::NX, Dynamics<DYN>::NU>& c,
-                                                const int k, const int l32, const int inst, const int vsel, double* jac_dump)
+                                                const int k, const int l32, const int inst, const int vsel, double* jac_dump, double* wq = nullptr)
 {
     using Dy = Dynamics<DYN>;
     constexpr int NX = Dy::NX, NU = Dy::NU, S = NX + NU, NC = Dy::NC;
@@ -3261,7 +3292,58 @@ __device__ __forceinline__ void big_stage_edges(const FactorParams& p, const Swe
             for (int t = 0; t < NU; ++t)
                 if (!isx && e - NX == t) w = sp.mp.sr[t];
             if (sp.refvec && isx) ref = sp.refvec[xo + v];   // time-varying state references
-            if (!ci.fixed && ci.cost_joff >= 0) {
+            bool wcol = false;
+            if constexpr (WD) {
+                // dense weight: column cc of the cost block C = d U (x - ref) / dx by central differences of U applied to the perturbed difference, in the
+                // reference's in-place order (the small family's DENSE path: a = x + delta, b = a - 2 delta); its Gram diagonal and gradient go where the
+                // single-entry row's go (dg / gd: the first damping sees them), the column to LDS for the off-diagonal entries (big_assemble_stage).
+                // A diagonal U gives the single-entry row's numbers bit for bit (every other product is an exact zero).
+                const int cls = isx ? (fin ? 2 : 0) : 1;
+                if ((sp.mp.wdense_mask >> cls) & 1) {
+                    wcol = true;
+                    constexpr int DM = NX, WDS = wdense_stride(NX);   // (NU <= NX in this family)
+                    const int dim = isx ? NX : NU, cc = isx ? e : e - NX, base = k * S + (isx ? 0 : NX);
+                    double col[DM];
+#pragma unroll
+                    for (int r = 0; r < DM; ++r) col[r] = 0.0;
+                    if (!ci.fixed && ci.cost_joff >= 0) {
+                        const double* U = sp.mp.wdense + WDS * cls;
+                        double xd[DM];
+#pragma unroll
+                        for (int j = 0; j < DM; ++j) {
+                            double rj = 0.0;
+                            if (isx && j < dim) rj = sp.refvec ? sp.refvec[xo + base + j] : sp.xref[(size_t)inst * CORBO_HIP_MAX_NX + j];
+                            xd[j] = (j < dim) ? X[base + j] - rj : 0.0;
+                        }
+                        const double a = xv + delta, b = a + neg2delta;
+#pragma unroll
+                        for (int r = 0; r < DM; ++r) {
+                            if (r < dim) {
+                                double x2[DM], x1[DM];
+#pragma unroll
+                                for (int j = 0; j < DM; ++j) { x2[j] = (j == cc) ? a - ref : xd[j]; x1[j] = (j == cc) ? b - ref : xd[j]; }
+                                // (the sweep's value of row r, incl. its `odd` column order for three columns on an odd residual row: sweep_body comp_values)
+                                const double val = dense_weight_row<DM>(U, r, dim, xd, ((ci.cost_row - cc) & 1) != 0);
+                                col[r] = scalar * (dense_weight_row<DM>(U, r, dim, x2) - dense_weight_row<DM>(U, r, dim, x1));
+                                dd += col[r] * col[r];
+                                gg -= col[r] * val;
+                            }
+                        }
+                    }
+                    double* blk = isx ? wq : wq + NX * NX;
+#pragma unroll
+                    for (int r = 0; r < DM; ++r)
+                        if (r < dim) blk[r * dim + cc] = col[r];
+                    // (the parity hook's copy in a block of its own, behind a compiler barrier: see the free-dt column of the shooting branch)
+                    asm volatile("" ::: "memory");
+                    if (jac_dump && !ci.fixed && ci.cost_joff >= 0) {
+#pragma unroll
+                        for (int r = 0; r < DM; ++r)
+                            if (r < dim) jac_dump[ci.cost_joff - cc + r] = col[r];
+                    }
+                }
+            }
+            if (!wcol && !ci.fixed && ci.cost_joff >= 0) {
                 const double a = xv + delta, b = a + neg2delta;
                 const double dv  = scalar * (w * (a - ref) - w * (b - ref));
                 const double val = w * (xv - ref);
@@ -3325,7 +3407,8 @@ __device__ __forceinline__ void big_stage_edges(const FactorParams& p, const Swe
 }
 #pragma clang fp contract(fast)
 
-template <int DYN, bool USE_MFMA, int DEFECT = CORBO_HIP_DEFECT_RK4_SHOOTING, bool ARROW = false, bool USERINEQ = false>
+// WD: non-diagonal weights -- an instantiation of its own (the diagonal problems' kernels are what they were), the dense cost blocks in LDS behind BigLds::TOTAL
+template <int DYN, bool USE_MFMA, int DEFECT = CORBO_HIP_DEFECT_RK4_SHOOTING, bool ARROW = false, bool USERINEQ = false, bool WD = false>
 __global__ __launch_bounds__(64)
 __attribute__((amdgpu_waves_per_eu(3, 3)))   // 168 registers: three waves per SIMD (170 without the cap, i.e. two; a cap of four spills 270 bytes and loses)
 void big_stage_kernel(const FactorParams p, const SweepParams sp, const int diag_only, double* jac_dump)
@@ -3350,24 +3433,30 @@ void big_stage_kernel(const FactorParams p, const SweepParams sp, const int diag
     // The first factorisation of a solve needs every stage's diag(J^T J) before any block can be damped (mu = tau max diag, :117): two passes of this
     // kernel.  The diag pass leaves the wave's LDS context -- the finite-difference Jacobians of its two intervals, 6.8 KB -- in HBM and the assembly
     // pass reads it back instead of integrating the 64 perturbed Runge-Kutta steps a second time (same numbers: bit-identical).
+    constexpr int CW = WD ? big_wd_doubles(NX, NU) : 0;   // (WD: the two intervals' dense cost blocks, cached behind the halves)
+    double* const wq0 = sm + BL::TOTAL;
     double2* const cache = (p.stage_cache && !jac_dump && p.first_pass)
-                               ? reinterpret_cast<double2*>(p.stage_cache + (size_t)inst * p.stage_cache_stride + (size_t)pair * 2 * BL::HALF) : nullptr;
+                               ? reinterpret_cast<double2*>(p.stage_cache + (size_t)inst * p.stage_cache_stride + (size_t)pair * 2 * (BL::HALF + CW)) : nullptr;
     const bool cached = cache && !diag_only && st->first;
     if (cached) {
         for (int i = lane; i < BL::HALF; i += 64) reinterpret_cast<double2*>(sm)[i] = cache[i];
+        if constexpr (WD) { for (int i = lane; i < CW; i += 64) reinterpret_cast<double2*>(wq0)[i] = cache[BL::HALF + i]; }
     }
     else
-    big_stage_edges<DYN, DEFECT, ARROW, USERINEQ>(p, sp, half ? c1 : c0, 2 * pair + half, lane & 31, inst, vsel, jac_dump ? jac_dump + (size_t)inst * sp.nnz_pad : nullptr);
+    big_stage_edges<DYN, DEFECT, ARROW, USERINEQ, WD>(p, sp, half ? c1 : c0, 2 * pair + half, lane & 31, inst, vsel, jac_dump ? jac_dump + (size_t)inst * sp.nnz_pad : nullptr,
+                                                      WD ? wq0 + half * CW : nullptr);
     __syncthreads();
     if (jac_dump) return;
-    if (cache && diag_only)
+    if (cache && diag_only) {
         for (int i = lane; i < BL::HALF; i += 64) cache[i] = reinterpret_cast<const double2*>(sm)[i];
+        if constexpr (WD) { for (int i = lane; i < CW; i += 64) cache[BL::HALF + i] = reinterpret_cast<const double2*>(wq0)[i]; }
+    }
     for (int h = 0; h < 2; ++h) {
         const int k = 2 * pair + h;
         if (k >= p.N) break;
         double* wk = p.work + (size_t)inst * p.work_stride + (size_t)k * BL::WS_STAGE;
         if (diag_only) big_diag_stage<NX, NU, DENSEC, ARROW>(h ? c1 : c0, p.N, k, lane, wk + BL::WS_L);
-        else big_assemble_stage<NX, NU, USE_MFMA, DENSEC, ARROW>(h ? c1 : c0, p.N, k, lane, wk, mu_eff);
+        else big_assemble_stage<NX, NU, USE_MFMA, DENSEC, ARROW, WD>(h ? c1 : c0, p.N, k, lane, wk, mu_eff, WD ? wq0 + h * CW : nullptr, WD ? p.wdense_mask : 0);
     }
 }
 
@@ -5007,6 +5096,10 @@ void launch_sweep_t(const SweepParams& p, hipStream_t stream)
         }
     }
     if constexpr (Dynamics<DYN>::NX > 4) {
+        if (p.mp.wdense) {   // non-diagonal weights (corbo_hip_create_weighted): residual only -- the Jacobian is big_stage_kernel's (no band route, no sweep Jacobian)
+            if (p.mode == 0 || (p.skip_jac && p.mode >= 2)) launch_sweep_wd<DYN, DEFECT>(p, stream);
+            return;   // (a sweep Jacobian on such a handle: refused by the host before it gets here, corbo_hip.hip wd_big_needs_sweep_jacobian)
+        }
         if (p.n_xedges > 0) {   // big-block family with extra edges (the band factorisation reads the stored Jacobian): the XE instantiation
             hipLaunchKernelGGL((sweep_kernel<DYN, DEFECT, false, false, true>), dim3(p.batch), dim3(SWEEP_THREADS), sweep_lds_bytes(p, Dynamics<DYN>::NC), stream, p);
             return;
@@ -5831,6 +5924,7 @@ bool CORBO_HIP_CAT(stage_entry_, CORBO_HIP_DYN_TU_NAME)(const FactorParams& fp, 
 {
     using Dy = Dynamics<CORBO_HIP_DYN_TU>;
     if (!sp.xe0 || (!fp.work && !jac_dump)) return false;
+    if (fp.wdense_mask) return launch_stage_wd<CORBO_HIP_DYN_TU>(fp, sp, diag_only, jac_dump, stream);   // non-diagonal weights
     const size_t lds = sizeof(double) * (size_t)BigLds<Dy::NX, Dy::NU>::TOTAL;
     const dim3 g((fp.N + 1) / 2, fp.batch), b(64);
     // (a user state function as the stage inequality -- csrc/stage_functions/, only where one is registered for this state dimension -- : the USERINEQ instantiation)
@@ -5940,6 +6034,49 @@ bool CORBO_HIP_CAT(stage_entry_, CORBO_HIP_DYN_TU_NAME)(const FactorParams&, con
 bool CORBO_HIP_CAT(factor_entry_, CORBO_HIP_DYN_TU_NAME)(const FactorParams&, const SweepParams&, hipStream_t) { return false; }
 #endif
 #endif  // CORBO_HIP_DYN_TU_PART 0 / 3
+// -DCORBO_HIP_DYN_TU_PART=4 (big-block models; the build compiles the model's other entries with -DCORBO_HIP_DYN_TU_SPLIT_WD): the non-diagonal weights'
+// instantiations -- the residual-only DENSE sweep and the WD stage kernels for the fixed-dt grids (shooting with Runge-Kutta 4 and lower, the four
+// collocation formulas; structure.cpp refuses the free-dt grids, Runge-Kutta 5 - 7 and extra edges with such weights)
+#if defined(CORBO_HIP_DYN_TU_BIG) && (CORBO_HIP_DYN_TU_PART == 4 || (CORBO_HIP_DYN_TU_PART == 0 && !defined(CORBO_HIP_DYN_TU_SPLIT_WD)))
+template <int DYN, int DEFECT>
+void launch_sweep_wd(const SweepParams& p, hipStream_t stream)
+{
+    hipLaunchKernelGGL((sweep_kernel<DYN, DEFECT, true, false, false, true>), dim3(p.batch), dim3(SWEEP_THREADS), sweep_lds_bytes(p, Dynamics<DYN>::NC), stream, p);
+}
+template void launch_sweep_wd<CORBO_HIP_DYN_TU, CORBO_HIP_DEFECT_RK4_SHOOTING>(const SweepParams&, hipStream_t);
+template void launch_sweep_wd<CORBO_HIP_DYN_TU, CORBO_HIP_DEFECT_FORWARD>(const SweepParams&, hipStream_t);
+template void launch_sweep_wd<CORBO_HIP_DYN_TU, CORBO_HIP_DEFECT_BACKWARD>(const SweepParams&, hipStream_t);
+template void launch_sweep_wd<CORBO_HIP_DYN_TU, CORBO_HIP_DEFECT_MIDPOINT>(const SweepParams&, hipStream_t);
+template void launch_sweep_wd<CORBO_HIP_DYN_TU, CORBO_HIP_DEFECT_CRANK_NICOLSON>(const SweepParams&, hipStream_t);
+
+template <int DYN>
+bool launch_stage_wd(const FactorParams& fp, const SweepParams& sp, int diag_only, double* jac_dump, hipStream_t stream)
+{
+    using Dy = Dynamics<DYN>;
+    if (fp.dt_free || (int)sp.mp.dyn[7] >= 5) return false;   // (refused at create)
+    const size_t lds = sizeof(double) * ((size_t)BigLds<Dy::NX, Dy::NU>::TOTAL + 2 * (size_t)big_wd_doubles(Dy::NX, Dy::NU));
+    const dim3 g((fp.N + 1) / 2, fp.batch), b(64);
+    const bool user_ineq = has_user_state_ineq<Dy::NX>() && sp.mp.ineq_id >= CORBO_HIP_STAGE_FN_USER;
+    auto go = [&](auto defect_tag) {
+        constexpr int DEFECT_ = decltype(defect_tag)::value;
+        if constexpr (has_user_state_ineq<Dy::NX>()) {
+            if (user_ineq) { hipLaunchKernelGGL((big_stage_kernel<DYN, true, DEFECT_, false, true, true>), g, b, lds, stream, fp, sp, diag_only, jac_dump); return true; }
+        }
+        hipLaunchKernelGGL((big_stage_kernel<DYN, true, DEFECT_, false, false, true>), g, b, lds, stream, fp, sp, diag_only, jac_dump);
+        return true;
+    };
+    (void)user_ineq;
+    switch (fp.defect) {
+        case CORBO_HIP_DEFECT_RK4_SHOOTING: return go(std::integral_constant<int, CORBO_HIP_DEFECT_RK4_SHOOTING>{});
+        case CORBO_HIP_DEFECT_FORWARD: return go(std::integral_constant<int, CORBO_HIP_DEFECT_FORWARD>{});
+        case CORBO_HIP_DEFECT_BACKWARD: return go(std::integral_constant<int, CORBO_HIP_DEFECT_BACKWARD>{});
+        case CORBO_HIP_DEFECT_MIDPOINT: return go(std::integral_constant<int, CORBO_HIP_DEFECT_MIDPOINT>{});
+        case CORBO_HIP_DEFECT_CRANK_NICOLSON: return go(std::integral_constant<int, CORBO_HIP_DEFECT_CRANK_NICOLSON>{});
+        default: return false;
+    }
+}
+template bool launch_stage_wd<CORBO_HIP_DYN_TU>(const FactorParams&, const SweepParams&, int, double*, hipStream_t);
+#endif
 #endif  // CORBO_HIP_DYN_TU
 
 #ifndef CORBO_HIP_DYN_TU
@@ -7034,7 +7171,8 @@ size_t big_stage_cache_doubles(const corbo_hip_problem_desc& d, int N)
 {
     if (!big_family_dims(d.nx, d.nu)) return 0;
     const int half = (5 * d.nx + 2 * (d.nx + d.nu) + d.nx * (d.nx + d.nu) + 8 + d.nx * d.nx + 1) & ~1;   // BigLds::HALF (checked there)
-    return (size_t)((N + 1) / 2) * 2 * (size_t)half;
+    const int wd   = d.weights_dense ? big_wd_doubles(d.nx, d.nu) : 0;   // (non-diagonal weights, corbo_hip_create_weighted: the dense cost blocks of big_stage_kernel<.., WD>)
+    return (size_t)((N + 1) / 2) * 2 * (size_t)(half + wd);
 }
 
 bool launch_factor(const corbo_hip_problem_desc& d, const FactorParams& p, hipStream_t stream, const SweepParams* sp)

@@ -231,6 +231,10 @@ bool launch_sweep(const corbo_hip_problem_desc& d, const SweepParams& p, hipStre
 // LDS-resident small-block families
 bool launch_factor(const corbo_hip_problem_desc& d, const FactorParams& p, hipStream_t stream, const SweepParams* sp = nullptr);
 size_t big_stage_cache_doubles(const corbo_hip_problem_desc& d, int N);   // per instance (0: not a big-block descriptor)
+// big-block family with non-diagonal weights (corbo_hip_create_weighted): the residual-only DENSE sweep and the WD stage kernels, defined in a unit of
+// their own per model (kernels.hip, CORBO_HIP_DYN_TU_PART 4) -- the model's other unit keeps its kernels and its compile time
+template <int DYN, int DEFECT> void launch_sweep_wd(const SweepParams& p, hipStream_t stream);
+template <int DYN> bool launch_stage_wd(const FactorParams& fp, const SweepParams& sp, int diag_only, double* jac_dump, hipStream_t stream);
 // one fused LM pass: [sweep phase (sp.mode 2 = prologue, 3 = trial step) -> factor phase] per workgroup, one launch
 struct WarmStartParams {
     int32_t batch, nvs, nx, nu, N, xf_fixed_mask, shift;

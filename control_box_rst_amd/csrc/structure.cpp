@@ -373,6 +373,64 @@ std::string build_structure(const corbo_hip_problem_desc& d, Structure& S)
     return "";
 }
 
+std::string validate_weight_factors(const corbo_hip_problem_desc& d, const corbo_hip_weight_factors& w)
+{
+    if (d.weights_dense) return "corbo_hip_create_weighted: desc.weights_dense must be 0 when the factors come in a corbo_hip_weight_factors (one source of truth)";
+    std::string err = validate_desc(d);
+    if (!err.empty()) return err;
+    if (w.mask < 0 || w.mask > 7) return "weight factors: mask bits 0..2";
+    if (!w.mask) return "";
+    if (d.nx > 4 && !big_family_dims(d.nx, d.nu)) return "non-diagonal weights: families with nx <= 4, and the big-block family";
+    if (d.cost_nonlsq) return "non-diagonal weights: least-squares form only (cost_nonlsq = 0)";
+    if ((w.mask & 3) && !(CORBO_HIP_COST_TERMS(d.stage_cost) & 3)) return "weight factors: mask bits 0 / 1 without a quadratic stage cost";
+    if ((w.mask & 4) && !d.final_cost) return "weight factors: mask bit 2 without a final cost";
+    for (int i = 0; i < d.nx; ++i)
+        for (int j = 0; j < i; ++j)
+            if (((w.mask & 1) && w.q_sqrt[i * d.nx + j] != 0.0) || ((w.mask & 4) && w.qf_sqrt[i * d.nx + j] != 0.0))
+                return "q_sqrt / qf_sqrt must be upper triangular (Eigen::LLT<.., Upper>::matrixU())";
+    for (int i = 0; i < d.nu; ++i)
+        for (int j = 0; j < i; ++j)
+            if ((w.mask & 2) && w.r_sqrt[i * d.nu + j] != 0.0) return "r_sqrt must be upper triangular";
+    if (d.nx > 4) {   // what the big-block family's DENSE instantiations cover (kernels.hip, big_stage_kernel WD)
+        if (d.ctrl_dev || d.stage_ineq_integral || d.stage_eq || d.stage_ineq_control)
+            return "non-diagonal weights around a big-block model with extra edges (control-deviation term, integral-form constraints, a user control inequality): "
+                   "the band route has no dense-weight instantiation for nx > 4";
+        if (d.grid == CORBO_HIP_GRID_FD_VARIABLE || d.grid == CORBO_HIP_GRID_MS_VARIABLE)
+            return "non-diagonal weights around a big-block model on a free-dt grid (MultipleShootingVariableGrid / FiniteDifferencesVariableGrid): fixed-dt grids only";
+        if (d.shooting_integrator >= 5) return "non-diagonal weights around a big-block model with Runge-Kutta 5 - 7: shooting integrators up to Runge-Kutta 4";
+    }
+    return "";
+}
+
+std::string build_structure_weighted(const corbo_hip_problem_desc& d, const corbo_hip_weight_factors& w, Structure& S)
+{
+    std::string err = validate_weight_factors(d, w);
+    if (!err.empty()) return err;
+    if (d.nx <= 4) {   // the descriptor path: factors in the descriptor's own arrays (stride nx / nu), its rules apply
+        corbo_hip_problem_desc d2 = d;
+        d2.weights_dense = w.mask;
+        for (int i = 0; i < 16; ++i) {
+            const bool qi = i < d.nx * d.nx, ri = i < d.nu * d.nu;
+            d2.q_sqrt[i]  = ((w.mask & 1) && qi) ? w.q_sqrt[i] : 0.0;
+            d2.qf_sqrt[i] = ((w.mask & 4) && qi) ? w.qf_sqrt[i] : 0.0;
+            d2.r_sqrt[i]  = ((w.mask & 2) && ri) ? w.r_sqrt[i] : 0.0;
+        }
+        return build_structure(d2, S);
+    }
+    err = build_structure(d, S);   // (the structure does not depend on the weights: the reference lists full edge blocks either way)
+    if (!err.empty() || !w.mask) return err;
+    S.desc.weights_dense = w.mask;
+    const int st = wdense_stride(d.nx);
+    S.wside.assign(3 * (size_t)st, 0.0);
+    for (int i = 0; i < d.nx * d.nx; ++i) {
+        if (w.mask & 1) S.wside[i] = w.q_sqrt[i];
+        if (w.mask & 4) S.wside[2 * st + i] = w.qf_sqrt[i];
+    }
+    for (int i = 0; i < d.nu * d.nu; ++i)
+        if (w.mask & 2) S.wside[st + i] = w.r_sqrt[i];
+    return "";
+}
+
 void init_trajectory(const corbo_hip_problem_desc& d, int batch, const double* x0, const double* xf, double* x_out)
 {
     // FullDiscretizationGridBase::initializeSequences (full_discretization_grid_base.cpp:134-179):

@@ -106,6 +106,9 @@ struct Structure {
     std::vector<XEdge> xedges;           // integral-form constraint edges / control-deviation edges (empty for every other descriptor)
     int eq_stride = 0;                   // residual rows per interval in the equality section (nx; nx + 1 with an integral equality row)
     int eq_defect_off = 0;               // row of the dynamics defect inside the interval's equality rows (1 behind a LeftSumEqualityEdge)
+    // big-block family with non-diagonal weights (corbo_hip_create_weighted; desc.weights_dense holds the mask): the factors as the kernels read them,
+    // [Q | R | Qf] in blocks of wdense_stride(nx) = nx * nx doubles (R row-major with stride nu in the first nu * nu of its block); empty otherwise
+    std::vector<double> wside;
     bool has_extra() const { return !xedges.empty(); }
 
     int x_off(int k) const { return k * s; }             // k in [0, N-1]; k == N-1 is x_f
@@ -152,6 +155,12 @@ bool build_bt_tables(const Structure& S, const std::vector<int32_t>& jmap, int n
 // returns "" on success, otherwise an error text
 std::string validate_desc(const corbo_hip_problem_desc& d);
 std::string build_structure(const corbo_hip_problem_desc& d, Structure& out);
+// corbo_hip_create_weighted: the factors beside the descriptor (checked before any HIP call).  nx <= 4: the descriptor path's structure (factors moved
+// into q_sqrt / r_sqrt / qf_sqrt, weights_dense = mask); big-block family: Structure::wside
+std::string validate_weight_factors(const corbo_hip_problem_desc& d, const corbo_hip_weight_factors& w);
+std::string build_structure_weighted(const corbo_hip_problem_desc& d, const corbo_hip_weight_factors& w, Structure& out);
+// doubles per factor block of the device's weight table: 16 for the small-block families (the descriptor's arrays), nx * nx for the big-block family
+constexpr int wdense_stride(int nx) { return nx > 4 ? nx * nx : 16; }
 void init_trajectory(const corbo_hip_problem_desc& d, int batch, const double* x0, const double* xf, double* x_out);
 
 }  // namespace corbo_hip

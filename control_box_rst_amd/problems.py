@@ -252,3 +252,16 @@ SCENARIOS["par2"] = (lambda **kw: parallel_integrator_desc(2, **kw), BENCHMARK_W
 SCENARIOS["par3"] = (lambda **kw: parallel_integrator_desc(3, **kw), BENCHMARK_WEIGHTS)
 for _name in BENCHMARK_SYSTEMS:
     SCENARIOS[_name] = ((lambda n: (lambda **kw: benchmark_desc(n, **kw)))(_name), BENCHMARK_WEIGHTS)
+
+
+def upper_factor(W):
+    """Upper Cholesky factor U of a symmetric positive definite weight, W = U^T U: the transposed lower factor of numpy.linalg.cholesky (the factor the
+    reference keeps, Eigen::LLT<.., Upper>::matrixU(), quadratic_cost.cpp:36-55).  Its entries can differ from Eigen's in the last bit (another
+    summation order inside the factorisation); the device uses exactly the factor it is given -- for bit-level agreement with a reference run pass
+    that run's factor itself.  Entries below the diagonal are exact zeros."""
+    W = np.asarray(W, dtype=np.float64)
+    if W.ndim != 2 or W.shape[0] != W.shape[1]:
+        raise ValueError("upper_factor: a square matrix")
+    if not np.array_equal(W, W.T):
+        raise ValueError("upper_factor: the weight must be symmetric")
+    return np.triu(np.linalg.cholesky(W).T)

@@ -37,6 +37,35 @@ def get_dims(desc: ProblemDesc) -> Dims:
     return d
 
 
+def weight_factors(desc: ProblemDesc, weights) -> "capi.WeightFactors":
+    """capi.WeightFactors from a dict of full weights ("Q", "R", "Qf": symmetric positive definite) and / or upper factors ("Q_sqrt", "R_sqrt", "Qf_sqrt";
+    W = U^T U).  A full weight is factored by problems.upper_factor; the device uses the factor it is given."""
+    from . import problems
+    if isinstance(weights, capi.WeightFactors):
+        return weights
+    unknown = set(weights) - {"Q", "R", "Qf", "Q_sqrt", "R_sqrt", "Qf_sqrt"}
+    if unknown:   # (a misspelt key would leave the descriptor's diagonal weights in force without a word)
+        raise ValueError(f"weights: unknown keys {sorted(unknown)}; expected Q, R, Qf (full weights) or Q_sqrt, R_sqrt, Qf_sqrt (upper factors)")
+    w = capi.WeightFactors()
+    nx, nu = desc.nx, desc.nu
+    for bit, key, dim, field in ((0, "Q", nx, "q_sqrt"), (1, "R", nu, "r_sqrt"), (2, "Qf", nx, "qf_sqrt")):
+        U = None
+        if weights.get(key + "_sqrt") is not None:
+            U = np.asarray(weights[key + "_sqrt"], dtype=np.float64)
+        elif weights.get(key) is not None:
+            U = problems.upper_factor(weights[key])
+        if U is None:
+            continue
+        if U.shape != (dim, dim):
+            raise ValueError(f"weight {key}: shape {U.shape}, expected {(dim, dim)}")
+        arr = getattr(w, field)
+        for i in range(dim):
+            for j in range(dim):
+                arr[i * dim + j] = float(U[i, j])
+        w.mask |= 1 << bit
+    return w
+
+
 def get_structure(desc: ProblemDesc):
     lib = capi.load()
     d = get_dims(desc)
@@ -64,7 +93,7 @@ def init_trajectory(desc: ProblemDesc, x0, xf) -> np.ndarray:
 class BatchedLevenbergMarquardt:
     """LevenbergMarquardtSparse for `batch` independent instances of one hypergraph structure, on one MI355X."""
 
-    def __init__(self, desc: ProblemDesc, batch: int, device: int = 0, route: int = 0):
+    def __init__(self, desc: ProblemDesc, batch: int, device: int = 0, route: int = 0, weights=None):
         self.lib = capi.load()
         self.desc = desc
         self.batch = int(batch)
@@ -72,8 +101,13 @@ class BatchedLevenbergMarquardt:
         self.opts: LmOpts = capi.default_lm_opts()
         self.dims = get_dims(desc)
         self._h = C.c_void_p()
+        # weights: non-diagonal weights beside the descriptor (corbo_hip_create_weighted; the only way for nx > 4) -- a capi.WeightFactors, or a dict
+        # with any of "Q", "R", "Qf" (full symmetric positive definite matrices) / "Q_sqrt", "R_sqrt", "Qf_sqrt" (explicit upper factors)
+        self.weights = None if weights is None else weight_factors(desc, weights)
         # route: capi.ROUTE_* flags of corbo_hip_create_routed (A/B of two factorisation routes of one descriptor); 0 = the library's choice
-        if route:
+        if self.weights is not None:
+            rc = self.lib.corbo_hip_create_weighted(C.byref(desc), C.byref(self.weights), self.batch, self.device, int(route), C.byref(self._h))
+        elif route:
             rc = self.lib.corbo_hip_create_routed(C.byref(desc), self.batch, self.device, int(route), C.byref(self._h))
         else:
             rc = self.lib.corbo_hip_create(C.byref(desc), self.batch, self.device, C.byref(self._h))

@@ -187,7 +187,8 @@ typedef struct corbo_hip_problem_desc {
      * term is U (x - xref) / U u (quadratic_cost.cpp:116-118, 148-150; final_state_cost.cpp:88-90) -- a dense product in Eigen's gemv
      * order, its Jacobian block a dense (upper-triangular) nx x nx block.  Bit 0: q_sqrt is used instead of q_diag, bit 1: r_sqrt instead of
      * r_diag, bit 2: qf_sqrt instead of qf_diag.  Row-major [i * nx + j] (r_sqrt: [i * nu + j]), entries below the diagonal zero.  Families
-     * with nx <= 4 on the Levenberg-Marquardt path and the Hessian-path operators in least-squares form (cost_nonlsq = 0). */
+     * with nx <= 4 on the Levenberg-Marquardt path and the Hessian-path operators in least-squares form (cost_nonlsq = 0).  The big-block family
+     * (nx > 4, factors beyond 16 entries): corbo_hip_create_weighted with a corbo_hip_weight_factors, this field 0. */
     int32_t weights_dense;
     /* Integrator of the shooting grids' defect edges (MultipleShootingGrid::setNumericalIntegrator; explicit_integrators.h):
      * 0 = IntegratorExplicitRungeKutta4 (:244-295, what the reference's examples use), 1 = IntegratorExplicitEuler (:47-72),
@@ -319,6 +320,26 @@ int corbo_hip_create(const corbo_hip_problem_desc* desc, int batch, int device, 
 #define CORBO_HIP_ROUTE_FREE_DT_BAND 1u
 #define CORBO_HIP_ROUTE_XE_BAND      2u
 int corbo_hip_create_routed(const corbo_hip_problem_desc* desc, int batch, int device, uint32_t route, corbo_hip_handle* out);
+/* Non-diagonal weights of any family, given BESIDE the descriptor: the descriptor's q_sqrt / r_sqrt / qf_sqrt hold 16 doubles, a 12-state
+ * factor has 144.  Same meaning as corbo_hip_problem_desc::weights_dense and its factors: mask bit 0 Q, bit 1 R, bit 2 Qf; each factor the
+ * UPPER Cholesky factor U with W = U^T U, row-major [i * nx + j] (r_sqrt: [i * nu + j]), entries below the diagonal zero. */
+typedef struct corbo_hip_weight_factors {
+    int32_t mask;
+    int32_t reserved0;
+    double q_sqrt[CORBO_HIP_MAX_NX * CORBO_HIP_MAX_NX];
+    double r_sqrt[CORBO_HIP_MAX_NU * CORBO_HIP_MAX_NU];
+    double qf_sqrt[CORBO_HIP_MAX_NX * CORBO_HIP_MAX_NX];
+} corbo_hip_weight_factors;
+/* corbo_hip_create_routed with the weights' factors in `weights`.  weights == NULL: exactly corbo_hip_create_routed.  weights != NULL needs
+ * desc->weights_dense == 0 (one source of truth; else CORBO_HIP_ERR_INVALID).  Checked before any HIP call (CORBO_HIP_ERR_INVALID): upper-triangular
+ * factors, a mask bit only where a quadratic stage cost (bits 0, 1) or a final cost (bit 2) exists, least-squares form (cost_nonlsq = 0).
+ * Families with nx <= 4: the handle is the one of the descriptor path (the factors in q_sqrt / r_sqrt / qf_sqrt, weights_dense = mask) -- same
+ * kernels, same bytes.  Big-block family (5 <= nx <= 12): the Levenberg-Marquardt path on the fixed-dt grids (MultipleShootingGrid with Runge-Kutta 4 / 3 / 2
+ * or Euler, the four collocation formulas on the FiniteDifferencesGrid); refused with CORBO_HIP_ERR_INVALID and a named reason: free-dt grids, Runge-Kutta
+ * 5 - 7, extra edges (control-deviation term, integral-form constraints, a user control inequality).  On such a handle the operators of the exact-Hessian
+ * path (Hessians, objective gradient, linear form) return CORBO_HIP_ERR_UNSUPPORTED.  The Jacobian structure does not depend on the weights. */
+int corbo_hip_create_weighted(const corbo_hip_problem_desc* desc, const corbo_hip_weight_factors* weights, int batch, int device, uint32_t route,
+                              corbo_hip_handle* out);
 void corbo_hip_destroy(corbo_hip_handle h);
 /* Which factorisation a handle's solves run through (decided in corbo_hip_create from the descriptor's structure; for logs, A/B scripts and the route tests):
  *   CORBO_HIP_FACTOR_STAGE_CR     small-block families (nx <= 4): controls first, block cyclic reduction on the state blocks; one launch per solve up to 256 grid
@@ -619,7 +640,7 @@ int corbo_hip_set_option(corbo_hip_handle h, const char* name, int value);
 const char* corbo_hip_last_error(void);
 
 /* Layout check for bindings that mirror the PODs above by hand (ctypes, cgo, JNI ...): sizeof of what THIS library was compiled with --
- * which = 0: corbo_hip_problem_desc, 1: corbo_hip_dims, 2: corbo_hip_lm_opts, 3: corbo_hip_stats; anything else: 0.  A binding compares
+ * which = 0: corbo_hip_problem_desc, 1: corbo_hip_dims, 2: corbo_hip_lm_opts, 3: corbo_hip_stats, 4: corbo_hip_weight_factors; anything else: 0.  A binding compares
  * it with its own mirror when it loads the library and refuses on a mismatch (control_box_rst_amd/capi.py does). */
 size_t corbo_hip_sizeof(int which);
 
