@@ -14,7 +14,10 @@
 //
 // Both are table driven (structure.hpp); nothing here knows about edge objects.
 #include "kernels.hpp"
+#include <mutex>
+#include <set>
 #include <type_traits>
+#include <utility>
 
 namespace corbo_hip {
 
@@ -26,15 +29,58 @@ constexpr int LONG_HORIZON_MAX = 1024;
 constexpr double LM_EPS1 = 1e-5, LM_EPS2 = 1e-5, LM_EPS3 = 1e-5, LM_EPS4 = 0.0, LM_TAU = 1e-5;  // levenberg_marquardt_sparse.cpp:103-110
 constexpr int LM_MAX_INNER = 64;  // guard against an endless reject loop (the reference would spin)
 
-// hipFuncSetAttribute is per DEVICE and handles may live on several: a launcher's "already set" flag is one bit per device.
-inline bool first_on_device(unsigned long long& mask)
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device): attributes are per DEVICE, and handles may live on several
+// devices and be driven from several threads.  Only a successful call is remembered; a failed one's sticky error is cleared (the launch
+// that needs the attribute then reports its own failure).
+template <class K>
+void set_max_dynamic_lds(K kernel, int bytes)
 {
-    int d = 0;
-    (void)hipGetDevice(&d);
-    const unsigned long long bit = 1ull << (d & 63);
-    if (mask & bit) return false;
-    mask |= bit;
-    return true;
+    static std::mutex mu;
+    static std::set<std::pair<const void*, int>> done;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const std::pair<const void*, int> key(reinterpret_cast<const void*>(kernel), dev);
+    std::lock_guard<std::mutex> lock(mu);
+    if (done.count(key)) return;
+    if (hipFuncSetAttribute(key.first, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess) done.insert(key);
+    else (void)hipGetLastError();
+}
+
+// A runtime defect formula as a compile-time one: f(std::integral_constant<int, DEFECT>{}); false for a formula without kernels.
+template <class F>
+bool with_defect(int defect, F&& f)
+{
+    using std::integral_constant;
+    switch (defect) {
+        case CORBO_HIP_DEFECT_FORWARD: return f(integral_constant<int, CORBO_HIP_DEFECT_FORWARD>{});
+        case CORBO_HIP_DEFECT_BACKWARD: return f(integral_constant<int, CORBO_HIP_DEFECT_BACKWARD>{});
+        case CORBO_HIP_DEFECT_MIDPOINT: return f(integral_constant<int, CORBO_HIP_DEFECT_MIDPOINT>{});
+        case CORBO_HIP_DEFECT_CRANK_NICOLSON: return f(integral_constant<int, CORBO_HIP_DEFECT_CRANK_NICOLSON>{});
+        case CORBO_HIP_DEFECT_RK4_SHOOTING: return f(integral_constant<int, CORBO_HIP_DEFECT_RK4_SHOOTING>{});
+        default: return false;
+    }
+}
+// ... where shooting with Runge-Kutta 5 / 6 / 7 (slot 7 of the model parameters: the grid's integrator) is DEFECT_SHOOTING_HIGH, a formula
+// of its own (model.hpp)
+template <class F>
+bool with_defect(int defect, const double* dyn, F&& f)
+{
+    if (defect == CORBO_HIP_DEFECT_RK4_SHOOTING && (int)dyn[7] >= 5) return f(std::integral_constant<int, DEFECT_SHOOTING_HIGH>{});
+    return with_defect(defect, f);
+}
+
+// The small-block (nx, nu) shapes of the factor kernels: f(std::integral_constant<int, NX>{}, std::integral_constant<int, NU>{}), or `none`.
+template <class R, class F>
+R with_small_shape(int nx, int nu, R none, F&& f)
+{
+    using std::integral_constant;
+    if (nx == 2 && nu == 1) return f(integral_constant<int, 2>{}, integral_constant<int, 1>{});
+    if (nx == 3 && nu == 2) return f(integral_constant<int, 3>{}, integral_constant<int, 2>{});
+    if (nx == 3 && nu == 1) return f(integral_constant<int, 3>{}, integral_constant<int, 1>{});
+    if (nx == 4 && nu == 1) return f(integral_constant<int, 4>{}, integral_constant<int, 1>{});
+    if (nx == 2 && nu == 2) return f(integral_constant<int, 2>{}, integral_constant<int, 2>{});
+    if (nx == 3 && nu == 3) return f(integral_constant<int, 3>{}, integral_constant<int, 3>{});
+    return none;
 }
 
 // Workgroup barrier for hand-overs through LDS only.  __syncthreads() is a workgroup-scope release/acquire fence + s_barrier: the
@@ -5055,14 +5101,13 @@ bool launch_bt_t(const FactorParams& fp, const SweepParams& sp, hipStream_t stre
             grid = fp.queue_grid * per_cu;
             if (grid > fp.batch) grid = fp.batch;
         }
-        static unsigned long long attr_set[6] = {0, 0, 0, 0, 0, 0};   // (per device)
-        auto go = [&](auto kernel, int slot) {
-            if (first_on_device(attr_set[slot])) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        auto go = [&](auto kernel) {
+            set_max_dynamic_lds(kernel, 160 * 1024);
             hipLaunchKernelGGL(kernel, dim3(grid), dim3(BT_THREADS), lds, stream, fp, sp);
         };
-        if (big) { if (arrow) go(lm_bt_kernel<DYN, DEFECT, true, true, 1>, 3); else go(lm_bt_kernel<DYN, DEFECT, false, true, 1>, 2); }
-        else if (two) { if (arrow) go(lm_bt_kernel<DYN, DEFECT, true, false, 2>, 5); else go(lm_bt_kernel<DYN, DEFECT, false, false, 2>, 4); }
-        else { if (arrow) go(lm_bt_kernel<DYN, DEFECT, true, false, 3>, 1); else go(lm_bt_kernel<DYN, DEFECT, false, false, 3>, 0); }
+        if (big) { if (arrow) go(lm_bt_kernel<DYN, DEFECT, true, true, 1>); else go(lm_bt_kernel<DYN, DEFECT, false, true, 1>); }
+        else if (two) { if (arrow) go(lm_bt_kernel<DYN, DEFECT, true, false, 2>); else go(lm_bt_kernel<DYN, DEFECT, false, false, 2>); }
+        else { if (arrow) go(lm_bt_kernel<DYN, DEFECT, true, false, 3>); else go(lm_bt_kernel<DYN, DEFECT, false, false, 3>); }
         return true;
     }
 }
@@ -5120,23 +5165,16 @@ bool launch_sweep_d(int defect, const SweepParams& p, hipStream_t stream)
     launch_sweep_t<DYN, CORBO_HIP_DEFECT_CRANK_NICOLSON>(p, stream);
     return true;
 #else
-    if (defect == CORBO_HIP_DEFECT_RK4_SHOOTING && (int)p.mp.dyn[7] >= 5) {   // Runge-Kutta 5 / 6 / 7: a defect formula of its own (model.hpp)
-        if constexpr (Dynamics<DYN>::NX <= 4) { launch_sweep_t<DYN, DEFECT_SHOOTING_HIGH>(p, stream); return true; }
-        else {
+    return with_defect(defect, p.mp.dyn, [&](auto defect_tag) -> bool {
+        constexpr int DEFECT = decltype(defect_tag)::value;
+        if constexpr (DEFECT == DEFECT_SHOOTING_HIGH && Dynamics<DYN>::NX > 4) {
             // big-block family: the residual-only instantiation (the Jacobian of these handles is the stage kernel's; no band route with these integrators)
             if (p.n_xedges > 0 || !(p.mode == 0 || (p.skip_jac && p.mode >= 2))) return false;
             hipLaunchKernelGGL((sweep_kernel<DYN, DEFECT_SHOOTING_HIGH, false, false, false, true>), dim3(p.batch), dim3(SWEEP_THREADS), sweep_lds_bytes(p, Dynamics<DYN>::NC), stream, p);
-            return true;
         }
-    }
-    switch (defect) {
-        case CORBO_HIP_DEFECT_FORWARD: launch_sweep_t<DYN, CORBO_HIP_DEFECT_FORWARD>(p, stream); return true;
-        case CORBO_HIP_DEFECT_BACKWARD: launch_sweep_t<DYN, CORBO_HIP_DEFECT_BACKWARD>(p, stream); return true;
-        case CORBO_HIP_DEFECT_MIDPOINT: launch_sweep_t<DYN, CORBO_HIP_DEFECT_MIDPOINT>(p, stream); return true;
-        case CORBO_HIP_DEFECT_CRANK_NICOLSON: launch_sweep_t<DYN, CORBO_HIP_DEFECT_CRANK_NICOLSON>(p, stream); return true;
-        case CORBO_HIP_DEFECT_RK4_SHOOTING: launch_sweep_t<DYN, CORBO_HIP_DEFECT_RK4_SHOOTING>(p, stream); return true;
-        default: return false;
-    }
+        else launch_sweep_t<DYN, DEFECT>(p, stream);
+        return true;
+    });
 #endif
 }
 
@@ -5635,20 +5673,14 @@ void launch_hessian_t(const SweepParams& p, const HessParams& hp, hipStream_t st
 template <int DYN>
 bool launch_hessian_d(int defect, const SweepParams& p, const HessParams& hp, hipStream_t stream)
 {
-    {
-        if (defect == CORBO_HIP_DEFECT_RK4_SHOOTING && (int)p.mp.dyn[7] >= 5) {
-            if constexpr (Dynamics<DYN>::NX <= 4) { launch_hessian_t<DYN, DEFECT_SHOOTING_HIGH>(p, hp, stream); return true; }
-            else return false;
+    return with_defect(defect, p.mp.dyn, [&](auto defect_tag) -> bool {
+        constexpr int DEFECT = decltype(defect_tag)::value;
+        if constexpr (DEFECT == DEFECT_SHOOTING_HIGH && Dynamics<DYN>::NX > 4) return false;
+        else {
+            launch_hessian_t<DYN, DEFECT>(p, hp, stream);
+            return true;
         }
-        switch (defect) {
-            case CORBO_HIP_DEFECT_FORWARD: launch_hessian_t<DYN, CORBO_HIP_DEFECT_FORWARD>(p, hp, stream); return true;
-            case CORBO_HIP_DEFECT_BACKWARD: launch_hessian_t<DYN, CORBO_HIP_DEFECT_BACKWARD>(p, hp, stream); return true;
-            case CORBO_HIP_DEFECT_MIDPOINT: launch_hessian_t<DYN, CORBO_HIP_DEFECT_MIDPOINT>(p, hp, stream); return true;
-            case CORBO_HIP_DEFECT_CRANK_NICOLSON: launch_hessian_t<DYN, CORBO_HIP_DEFECT_CRANK_NICOLSON>(p, hp, stream); return true;
-            case CORBO_HIP_DEFECT_RK4_SHOOTING: launch_hessian_t<DYN, CORBO_HIP_DEFECT_RK4_SHOOTING>(p, hp, stream); return true;
-            default: return false;
-        }
-    }
+    });
 }
 
 template <int NX, int NU>
@@ -5719,15 +5751,11 @@ bool launch_pass_d(int defect, const FactorParams& fp, const SweepParams& sp, hi
     if (defect != CORBO_HIP_DEFECT_CRANK_NICOLSON) return false;
     return launch_pass_t<DYN, CORBO_HIP_DEFECT_CRANK_NICOLSON>(fp, sp, stream);
 #else
-    if (defect == CORBO_HIP_DEFECT_RK4_SHOOTING && (int)sp.mp.dyn[7] >= 5) return false;   // Runge-Kutta 5 / 6 / 7: separate launches only
-    switch (defect) {
-        case CORBO_HIP_DEFECT_FORWARD: return launch_pass_t<DYN, CORBO_HIP_DEFECT_FORWARD>(fp, sp, stream);
-        case CORBO_HIP_DEFECT_BACKWARD: return launch_pass_t<DYN, CORBO_HIP_DEFECT_BACKWARD>(fp, sp, stream);
-        case CORBO_HIP_DEFECT_MIDPOINT: return launch_pass_t<DYN, CORBO_HIP_DEFECT_MIDPOINT>(fp, sp, stream);
-        case CORBO_HIP_DEFECT_CRANK_NICOLSON: return launch_pass_t<DYN, CORBO_HIP_DEFECT_CRANK_NICOLSON>(fp, sp, stream);
-        case CORBO_HIP_DEFECT_RK4_SHOOTING: return launch_pass_t<DYN, CORBO_HIP_DEFECT_RK4_SHOOTING>(fp, sp, stream);
-        default: return false;
-    }
+    return with_defect(defect, sp.mp.dyn, [&](auto defect_tag) -> bool {
+        constexpr int DEFECT = decltype(defect_tag)::value;
+        if constexpr (DEFECT == DEFECT_SHOOTING_HIGH) return false;   // Runge-Kutta 5 / 6 / 7: separate launches only
+        else return launch_pass_t<DYN, DEFECT>(fp, sp, stream);
+    });
 #endif
 }
 
@@ -5741,18 +5769,17 @@ bool launch_factor_a(const FactorParams& p, hipStream_t stream)
         if (p.N > LONG_HORIZON_MAX || !p.work) return false;
         const size_t hyb = sizeof(double) * factor_long_hyb_lds_doubles<NX, NU>(p.N, ARROW);
         if (hyb + sizeof(LmState) + 64 <= (size_t)160 * 1024) {   // the state-block arrays fit the LDS of a CU: only the controls' arrays stay in the HBM workspace
-            static unsigned long long attr_set[4] = {0, 0, 0, 0};   // (per device)
-            auto go = [&](auto kernel, int slot, int threads) {
-                if (first_on_device(attr_set[slot])) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)sizeof(LmState) - 64);
+            auto go = [&](auto kernel, int threads) {
+                set_max_dynamic_lds(kernel, 160 * 1024 - (int)sizeof(LmState) - 64);
                 hipLaunchKernelGGL(kernel, dim3(p.batch), dim3(threads), hyb, stream, p);
             };
             const bool two_per_cu = 2 * (hyb + sizeof(LmState) + 64) <= (size_t)160 * 1024;
-            if (p.wdense_mask) go(factor_long_kernel<NX, NU, ARROW, true, true>, 1, 1024);
+            if (p.wdense_mask) go(factor_long_kernel<NX, NU, ARROW, true, true>, 1024);
             else if (p.N <= 512 && p.pass_threads != 1024) {   // (option pass_threads = 1024: the sixteen-wave shape, A/B)
-                if (two_per_cu) go(factor_long_kernel<NX, NU, ARROW, false, true, 512, 4>, 2, 512);
-                else go(factor_long_kernel<NX, NU, ARROW, false, true, 512, 2>, 3, 512);
+                if (two_per_cu) go(factor_long_kernel<NX, NU, ARROW, false, true, 512, 4>, 512);
+                else go(factor_long_kernel<NX, NU, ARROW, false, true, 512, 2>, 512);
             }
-            else go(factor_long_kernel<NX, NU, ARROW, false, true>, 0, 1024);
+            else go(factor_long_kernel<NX, NU, ARROW, false, true>, 1024);
             return true;
         }
         if (p.wdense_mask) hipLaunchKernelGGL((factor_long_kernel<NX, NU, ARROW, true>), dim3(p.batch), dim3(1024), 0, stream, p);   // non-diagonal weights
@@ -5836,53 +5863,20 @@ static void launch_plant_step_t(const PlantParams& p, hipStream_t stream)
 // ---------------------------------------------------------------------------------------------------------------------
 // Translation units.  This file is compiled once as the MAIN unit (CORBO_HIP_DYN_TU undefined): the kernels that do not depend on
 // the dynamics model (factor / big-block / warm start / helpers) and the dispatch; and once PER DYNAMICS MODEL with
-//   -DCORBO_HIP_DYN_TU=<template id> -DCORBO_HIP_DYN_TU_NAME=<suffix> [-DCORBO_HIP_DYN_TU_BIG]
-// : the sweep, fused-pass and plant kernels of that model behind three plain entry functions.  The models compile in parallel
-// (__graft_entry__.build()); a new model costs one more unit, not a longer critical path.
+//   -DCORBO_HIP_DYN_TU=<template id> -DCORBO_HIP_DYN_TU_NAME=<name> [-DCORBO_HIP_DYN_TU_BIG]
+// : that model's kernels behind six plain entry functions (sweep, fused pass, plant, Hessian; the big-block family's stage kernel and
+// factorisation -- the small-block models' return false).  The models are the rows of model_table.inc: __graft_entry__.build() makes
+// one unit per row, the main unit's dispatch (find_model) one table entry per row.  A new built-in model is its Dynamics<> specialisation
+// (model.hpp) and one row there; the units compile in parallel, so a new model costs one more unit, not a longer critical path.
 // ---------------------------------------------------------------------------------------------------------------------
-#define CORBO_HIP_DYN_ENTRIES(NAME)                                                                              \
-    bool sweep_entry_##NAME(int defect, const SweepParams& p, hipStream_t stream);                               \
-    bool pass_entry_##NAME(int defect, const FactorParams& fp, const SweepParams& sp, hipStream_t stream);       \
-    void plant_entry_##NAME(const PlantParams& p, hipStream_t stream);                                           \
-    bool hessian_entry_##NAME(int defect, const SweepParams& p, const HessParams& hp, hipStream_t stream);
-CORBO_HIP_DYN_ENTRIES(vdp)
-CORBO_HIP_DYN_ENTRIES(integ2)
-CORBO_HIP_DYN_ENTRIES(integ3)
-CORBO_HIP_DYN_ENTRIES(unicycle)
-CORBO_HIP_DYN_ENTRIES(quadrotor)
-CORBO_HIP_DYN_ENTRIES(duffing)
-CORBO_HIP_DYN_ENTRIES(rocket)
-CORBO_HIP_DYN_ENTRIES(pendulum)
-CORBO_HIP_DYN_ENTRIES(mpendulum)
-CORBO_HIP_DYN_ENTRIES(toy)
-CORBO_HIP_DYN_ENTRIES(artstein)
-CORBO_HIP_DYN_ENTRIES(cartpole)
-CORBO_HIP_DYN_ENTRIES(par2)
-CORBO_HIP_DYN_ENTRIES(par3)
-CORBO_HIP_DYN_ENTRIES(lin21)
-CORBO_HIP_DYN_ENTRIES(lin22)
-CORBO_HIP_DYN_ENTRIES(lin31)
-CORBO_HIP_DYN_ENTRIES(lin32)
-CORBO_HIP_DYN_ENTRIES(lin33)
-CORBO_HIP_DYN_ENTRIES(lin41)
-
-// user models (csrc/models/*.hpp, registry generated by the build): one set of entries each
-#if __has_include("models/_registry.inc")
-#define CORBO_HIP_USER_MODEL(NAME, SLOT, NX_, NU_, P0, P1, P2, P3) CORBO_HIP_DYN_ENTRIES(user_##NAME)
-#include "models/_registry.inc"
-#undef CORBO_HIP_USER_MODEL
-#endif
-
-// big-block family (5 <= nx <= 12; quadrotor and the user models of that size): stage kernel (Jacobian dump / assemble) and the factorisation
-#define CORBO_HIP_BIG_ENTRIES(NAME)                                                                                                       \
-    bool stage_entry_##NAME(const FactorParams& fp, const SweepParams& sp, int diag_only, double* jac_dump, hipStream_t stream);          \
+#define CORBO_HIP_MODEL(NAME, TID, PUBLIC, NX_, NU_)                                                                                    \
+    bool sweep_entry_##NAME(int defect, const SweepParams& p, hipStream_t stream);                                                     \
+    bool pass_entry_##NAME(int defect, const FactorParams& fp, const SweepParams& sp, hipStream_t stream);                             \
+    void plant_entry_##NAME(const PlantParams& p, hipStream_t stream);                                                                 \
+    bool hessian_entry_##NAME(int defect, const SweepParams& p, const HessParams& hp, hipStream_t stream);                             \
+    bool stage_entry_##NAME(const FactorParams& fp, const SweepParams& sp, int diag_only, double* jac_dump, hipStream_t stream);        \
     bool factor_entry_##NAME(const FactorParams& fp, const SweepParams& sp, hipStream_t stream);
-CORBO_HIP_BIG_ENTRIES(quadrotor)
-#if __has_include("models/_registry.inc")
-#define CORBO_HIP_USER_MODEL(NAME, SLOT, NX_, NU_, P0, P1, P2, P3) CORBO_HIP_BIG_ENTRIES(user_##NAME)
-#include "models/_registry.inc"
-#undef CORBO_HIP_USER_MODEL
-#endif
+#include "model_table.inc"
 
 #ifdef CORBO_HIP_DYN_TU
 #define CORBO_HIP_CAT2(a, b) a##b
@@ -5929,41 +5923,23 @@ bool CORBO_HIP_CAT(stage_entry_, CORBO_HIP_DYN_TU_NAME)(const FactorParams& fp, 
     const dim3 g((fp.N + 1) / 2, fp.batch), b(64);
     // (a user state function as the stage inequality -- csrc/stage_functions/, only where one is registered for this state dimension -- : the USERINEQ instantiation)
     const bool user_ineq = has_user_state_ineq<Dy::NX>() && sp.mp.ineq_id >= CORBO_HIP_STAGE_FN_USER;
-#define CORBO_HIP_STAGE_LAUNCH(DEFECT_, ARROW_)                                                                                                                             \
-    do {                                                                                                                                                                    \
-        if constexpr (has_user_state_ineq<Dy::NX>()) {                                                                                                                      \
-            if (user_ineq) { hipLaunchKernelGGL((big_stage_kernel<CORBO_HIP_DYN_TU, true, DEFECT_, ARROW_, true>), g, b, lds, stream, fp, sp, diag_only, jac_dump); return true; } \
-        }                                                                                                                                                                   \
-        hipLaunchKernelGGL((big_stage_kernel<CORBO_HIP_DYN_TU, true, DEFECT_, ARROW_, false>), g, b, lds, stream, fp, sp, diag_only, jac_dump);                             \
-        return true;                                                                                                                                                        \
-    } while (0)
     (void)user_ineq;
+    // shooting (Runge-Kutta 4 / 3 / 2, Euler; 5 / 6 / 7: an instantiation of its own), or a collocation formula on the FiniteDifferencesGrid
+    auto go = [&](auto defect_tag, auto arrow_tag) -> bool {
+        constexpr int DEFECT_ = decltype(defect_tag)::value;
+        constexpr bool ARROW_ = decltype(arrow_tag)::value;
+        if constexpr (has_user_state_ineq<Dy::NX>()) {
+            if (user_ineq) { hipLaunchKernelGGL((big_stage_kernel<CORBO_HIP_DYN_TU, true, DEFECT_, ARROW_, true>), g, b, lds, stream, fp, sp, diag_only, jac_dump); return true; }
+        }
+        hipLaunchKernelGGL((big_stage_kernel<CORBO_HIP_DYN_TU, true, DEFECT_, ARROW_, false>), g, b, lds, stream, fp, sp, diag_only, jac_dump);
+        return true;
+    };
     if (fp.dt_free) {   // free dt: the dt column of every defect edge and the border parts (second right-hand side of the chain)
         // (even block sizes only -- the partitioned chain carries the border)
         if constexpr (Dy::NX % 2 != 0) return false;
-        else
-        switch (fp.defect) {
-            case CORBO_HIP_DEFECT_RK4_SHOOTING:
-                if ((int)sp.mp.dyn[7] >= 5) CORBO_HIP_STAGE_LAUNCH(DEFECT_SHOOTING_HIGH, true);   // Runge-Kutta 5 / 6 / 7
-                else CORBO_HIP_STAGE_LAUNCH(CORBO_HIP_DEFECT_RK4_SHOOTING, true);
-            case CORBO_HIP_DEFECT_FORWARD: CORBO_HIP_STAGE_LAUNCH(CORBO_HIP_DEFECT_FORWARD, true);
-            case CORBO_HIP_DEFECT_BACKWARD: CORBO_HIP_STAGE_LAUNCH(CORBO_HIP_DEFECT_BACKWARD, true);
-            case CORBO_HIP_DEFECT_MIDPOINT: CORBO_HIP_STAGE_LAUNCH(CORBO_HIP_DEFECT_MIDPOINT, true);
-            case CORBO_HIP_DEFECT_CRANK_NICOLSON: CORBO_HIP_STAGE_LAUNCH(CORBO_HIP_DEFECT_CRANK_NICOLSON, true);
-            default: return false;
-        }
+        else return with_defect(fp.defect, sp.mp.dyn, [&](auto defect_tag) { return go(defect_tag, std::true_type{}); });
     }
-    switch (fp.defect) {   // shooting (Runge-Kutta 4 / 3 / 2, Euler; 5 / 6 / 7: an instantiation of its own), or a collocation formula on the FiniteDifferencesGrid
-        case CORBO_HIP_DEFECT_RK4_SHOOTING:
-            if ((int)sp.mp.dyn[7] >= 5) CORBO_HIP_STAGE_LAUNCH(DEFECT_SHOOTING_HIGH, false);
-            else CORBO_HIP_STAGE_LAUNCH(CORBO_HIP_DEFECT_RK4_SHOOTING, false);
-        case CORBO_HIP_DEFECT_FORWARD: CORBO_HIP_STAGE_LAUNCH(CORBO_HIP_DEFECT_FORWARD, false);
-        case CORBO_HIP_DEFECT_BACKWARD: CORBO_HIP_STAGE_LAUNCH(CORBO_HIP_DEFECT_BACKWARD, false);
-        case CORBO_HIP_DEFECT_MIDPOINT: CORBO_HIP_STAGE_LAUNCH(CORBO_HIP_DEFECT_MIDPOINT, false);
-        case CORBO_HIP_DEFECT_CRANK_NICOLSON: CORBO_HIP_STAGE_LAUNCH(CORBO_HIP_DEFECT_CRANK_NICOLSON, false);
-        default: return false;
-    }
-#undef CORBO_HIP_STAGE_LAUNCH
+    return with_defect(fp.defect, sp.mp.dyn, [&](auto defect_tag) { return go(defect_tag, std::false_type{}); });
 }
 // one factorisation of the big-block family: (first factorisation of a solve: diag pass + mu / stop) stage kernel, then the chain.  The
 // stacked chain kernel (big_chain2_kernel) is laid out for state blocks of 4, 8 or 12 rows; other sizes take the first formulation
@@ -5989,8 +5965,7 @@ bool CORBO_HIP_CAT(factor_entry_, CORBO_HIP_DYN_TU_NAME)(const FactorParams& p, 
             if (p.chain_variant == 6) nseg = 1;
             if (p.N < 4 * nseg) nseg = 1;
             auto launch3a = [&](auto kernel, int nseg_, size_t lds3) {
-                static unsigned long long attr_set[9] = {};   // (a kernel's attributes are per DEVICE: one bit per device, handles may live on several)
-                if (first_on_device(attr_set[nseg_])) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                set_max_dynamic_lds(kernel, 160 * 1024);
                 hipLaunchKernelGGL(kernel, dim3(p.batch), dim3(128 * nseg_), ((lds3 + 15) & ~(size_t)15) + sizeof(LmState), stream, p);
             };
             if (nseg == 4) launch3a(big_chain3_kernel<NX, NU, 4, true>, 4, sizeof(double) * (size_t)Chain3Lds<NX, NU, 4, true>::total(p.N));
@@ -6012,8 +5987,7 @@ bool CORBO_HIP_CAT(factor_entry_, CORBO_HIP_DYN_TU_NAME)(const FactorParams& p, 
             if (nseg > 0 && p.N < 4 * nseg) nseg = 0;   // (every segment needs a block of its own next to its separators)
             if (NX % 4 != 0 && nseg == 0) nseg = 1;     // (6- and 10-row blocks: the twisted chain's matrix-core tiling assumes multiples of four; one segment is the same elimination)
             auto launch3 = [&](auto kernel, int nseg_, size_t lds3) {
-                static unsigned long long attr_set[9] = {};   // (a kernel's attributes are per DEVICE: one bit per device, handles may live on several)
-                if (first_on_device(attr_set[nseg_])) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                set_max_dynamic_lds(kernel, 160 * 1024);
                 hipLaunchKernelGGL(kernel, dim3(p.batch), dim3(128 * nseg_), ((lds3 + 15) & ~(size_t)15) + sizeof(LmState), stream, p);
             };
             if (nseg == 4) launch3(big_chain3_kernel<NX, NU, 4>, 4, sizeof(double) * (size_t)Chain3Lds<NX, NU, 4>::total(p.N));
@@ -6029,7 +6003,7 @@ bool CORBO_HIP_CAT(factor_entry_, CORBO_HIP_DYN_TU_NAME)(const FactorParams& p, 
     else hipLaunchKernelGGL((big_chain_kernel<NX, NU, false>), dim3(p.batch), dim3(128), sizeof(double) * (4 * NX * NX + 2 * NX + 8), stream, p);
     return true;
 }
-#else   // small-block family: the dispatch tables name these entries for every user model
+#else   // small-block family: the dispatch table names these entries for every model
 bool CORBO_HIP_CAT(stage_entry_, CORBO_HIP_DYN_TU_NAME)(const FactorParams&, const SweepParams&, int, double*, hipStream_t) { return false; }
 bool CORBO_HIP_CAT(factor_entry_, CORBO_HIP_DYN_TU_NAME)(const FactorParams&, const SweepParams&, hipStream_t) { return false; }
 #endif
@@ -6066,14 +6040,7 @@ bool launch_stage_wd(const FactorParams& fp, const SweepParams& sp, int diag_onl
         return true;
     };
     (void)user_ineq;
-    switch (fp.defect) {
-        case CORBO_HIP_DEFECT_RK4_SHOOTING: return go(std::integral_constant<int, CORBO_HIP_DEFECT_RK4_SHOOTING>{});
-        case CORBO_HIP_DEFECT_FORWARD: return go(std::integral_constant<int, CORBO_HIP_DEFECT_FORWARD>{});
-        case CORBO_HIP_DEFECT_BACKWARD: return go(std::integral_constant<int, CORBO_HIP_DEFECT_BACKWARD>{});
-        case CORBO_HIP_DEFECT_MIDPOINT: return go(std::integral_constant<int, CORBO_HIP_DEFECT_MIDPOINT>{});
-        case CORBO_HIP_DEFECT_CRANK_NICOLSON: return go(std::integral_constant<int, CORBO_HIP_DEFECT_CRANK_NICOLSON>{});
-        default: return false;
-    }
+    return with_defect(fp.defect, go);
 }
 template bool launch_stage_wd<CORBO_HIP_DYN_TU>(const FactorParams&, const SweepParams&, int, double*, hipStream_t);
 #endif
@@ -6105,42 +6072,35 @@ __global__ __launch_bounds__(256) void broadcast_rows_kernel(const double* __res
     }
 }
 
+// The dispatch table: one entry per row of model_table.inc (built-in and user models), found by (public id, nx, nu).
+struct ModelEntries {
+    int dynamics, nx, nu;
+    bool (*sweep)(int defect, const SweepParams& p, hipStream_t stream);
+    bool (*pass)(int defect, const FactorParams& fp, const SweepParams& sp, hipStream_t stream);
+    void (*plant)(const PlantParams& p, hipStream_t stream);
+    bool (*hessian)(int defect, const SweepParams& p, const HessParams& hp, hipStream_t stream);
+    bool (*stage)(const FactorParams& fp, const SweepParams& sp, int diag_only, double* jac_dump, hipStream_t stream);
+    bool (*factor)(const FactorParams& fp, const SweepParams& sp, hipStream_t stream);
+};
+
+static const ModelEntries* find_model(const corbo_hip_problem_desc& d)
+{
+    static const ModelEntries table[] = {
+#define CORBO_HIP_MODEL(NAME, TID, PUBLIC, NX_, NU_) \
+    {PUBLIC, NX_, NU_, sweep_entry_##NAME, pass_entry_##NAME, plant_entry_##NAME, hessian_entry_##NAME, stage_entry_##NAME, factor_entry_##NAME},
+#include "model_table.inc"
+    };
+    for (const ModelEntries& m : table)
+        if (m.dynamics == d.dynamics && m.nx == d.nx && m.nu == d.nu) return &m;
+    return nullptr;
+}
+
 bool launch_plant_step(const corbo_hip_problem_desc& d, const PlantParams& p, hipStream_t stream)
 {
-#if __has_include("models/_registry.inc")
-#define CORBO_HIP_USER_MODEL(NAME, SLOT, NX_, NU_, P0, P1, P2, P3) if (d.dynamics == CORBO_HIP_DYN_USER + SLOT) { plant_entry_user_##NAME(p, stream); return true; }
-#include "models/_registry.inc"
-#undef CORBO_HIP_USER_MODEL
-#endif
-    switch (d.dynamics) {
-        case CORBO_HIP_DYN_VAN_DER_POL: plant_entry_vdp(p, stream); return true;
-        case CORBO_HIP_DYN_SERIAL_INTEGRATOR:
-            if (d.nx == 3) { plant_entry_integ3(p, stream); return true; }
-            if (d.nx != 2) return false;
-            plant_entry_integ2(p, stream);
-            return true;
-        case CORBO_HIP_DYN_UNICYCLE: plant_entry_unicycle(p, stream); return true;
-        case CORBO_HIP_DYN_QUADROTOR: plant_entry_quadrotor(p, stream); return true;
-        case CORBO_HIP_DYN_DUFFING: plant_entry_duffing(p, stream); return true;
-        case CORBO_HIP_DYN_FREE_SPACE_ROCKET: plant_entry_rocket(p, stream); return true;
-        case CORBO_HIP_DYN_SIMPLE_PENDULUM: plant_entry_pendulum(p, stream); return true;
-        case CORBO_HIP_DYN_MASSLESS_PENDULUM: plant_entry_mpendulum(p, stream); return true;
-        case CORBO_HIP_DYN_TOY_EXAMPLE: plant_entry_toy(p, stream); return true;
-        case CORBO_HIP_DYN_ARTSTEINS_CIRCLE: plant_entry_artstein(p, stream); return true;
-        case CORBO_HIP_DYN_CART_POLE: plant_entry_cartpole(p, stream); return true;
-        case CORBO_HIP_DYN_PARALLEL_INTEGRATOR:
-            if (d.nx == 2) plant_entry_par2(p, stream); else plant_entry_par3(p, stream);
-            return true;
-        case CORBO_HIP_DYN_LINEAR_STATE_SPACE:
-            if (d.nx == 2 && d.nu == 1) { plant_entry_lin21(p, stream); return true; }
-            if (d.nx == 2 && d.nu == 2) { plant_entry_lin22(p, stream); return true; }
-            if (d.nx == 3 && d.nu == 1) { plant_entry_lin31(p, stream); return true; }
-            if (d.nx == 3 && d.nu == 2) { plant_entry_lin32(p, stream); return true; }
-            if (d.nx == 3 && d.nu == 3) { plant_entry_lin33(p, stream); return true; }
-            if (d.nx == 4 && d.nu == 1) { plant_entry_lin41(p, stream); return true; }
-            return false;
-        default: return false;
-    }
+    const ModelEntries* m = find_model(d);
+    if (!m) return false;
+    m->plant(p, stream);
+    return true;
 }
 
 __global__ __launch_bounds__(256) void gather_first_control_kernel(const double* __restrict__ x, double* __restrict__ out, int nvs, int nx, int nu,
@@ -6268,12 +6228,9 @@ size_t factor_work_doubles(const corbo_hip_problem_desc& d)
     if (big_family_dims(d.nx, d.nu)) return (size_t)d.N * big_ws_stage(d.nx, d.nu);
     if (d.N > LONG_HORIZON && d.N <= LONG_HORIZON_MAX) {   // small-block families, long horizon: the factor carve lives in HBM
         const bool arrow = (d.grid == CORBO_HIP_GRID_FD_VARIABLE || d.grid == CORBO_HIP_GRID_MS_VARIABLE);
-        if (d.nx == 2 && d.nu == 1) return factor_long_work_doubles<2, 1>(d.N, arrow);
-        if (d.nx == 3 && d.nu == 2) return factor_long_work_doubles<3, 2>(d.N, arrow);
-        if (d.nx == 3 && d.nu == 1) return factor_long_work_doubles<3, 1>(d.N, arrow);
-        if (d.nx == 4 && d.nu == 1) return factor_long_work_doubles<4, 1>(d.N, arrow);
-        if (d.nx == 2 && d.nu == 2) return factor_long_work_doubles<2, 2>(d.N, arrow);
-        if (d.nx == 3 && d.nu == 3) return factor_long_work_doubles<3, 3>(d.N, arrow);
+        return with_small_shape(d.nx, d.nu, (size_t)0, [&](auto nx, auto nu) {
+            return factor_long_work_doubles<decltype(nx)::value, decltype(nu)::value>(d.N, arrow);
+        });
     }
     return 0;
 }
@@ -6282,162 +6239,43 @@ size_t factor_lds_bytes(const corbo_hip_problem_desc& d, const FactorParams& p)
 {
     if (big_family_dims(d.nx, d.nu)) return sizeof(double) * big_lds_total(d.nx, d.nu);
     const bool arrow = (d.grid == CORBO_HIP_GRID_FD_VARIABLE || d.grid == CORBO_HIP_GRID_MS_VARIABLE);
-    if (d.nx == 2 && d.nu == 1) return factor_lds<2, 1>(p.N, arrow);
-    if (d.nx == 3 && d.nu == 2) return factor_lds<3, 2>(p.N, arrow);
-    if (d.nx == 3 && d.nu == 1) return factor_lds<3, 1>(p.N, arrow);
-    if (d.nx == 4 && d.nu == 1) return factor_lds<4, 1>(p.N, arrow);
-    if (d.nx == 2 && d.nu == 2) return factor_lds<2, 2>(p.N, arrow);
-    if (d.nx == 3 && d.nu == 3) return factor_lds<3, 3>(p.N, arrow);
-    return 0;
+    return with_small_shape(d.nx, d.nu, (size_t)0, [&](auto nx, auto nu) { return factor_lds<decltype(nx)::value, decltype(nu)::value>(p.N, arrow); });
 }
 
-// Host-only mirror of the launch_sweep / launch_pass / launch_factor dispatch below: is there a device kernel set for this
-// (dynamics, nx, nu, defect, grid)?  corbo_hip_create refuses a descriptor at once instead of failing in the first solve.
+// Is there a device kernel set for this (dynamics, nx, nu, defect, grid)?  corbo_hip_create refuses a descriptor at once instead of
+// failing in the first solve.  The big-block family runs on the shooting grids (explicit integrators) or the collocation grids (the four
+// formulas); with a fixed dt the stage / chain kernels, with a free dt (...VariableGrid) the sweep kernel's stored Jacobian and the band
+// factorisation (corbo_hip_create, band_route).
 bool device_kernels_exist(const corbo_hip_problem_desc& d)
 {
     const bool known_defect = d.defect >= CORBO_HIP_DEFECT_FORWARD && d.defect <= CORBO_HIP_DEFECT_RK4_SHOOTING;
-    if (!known_defect) return false;
-    auto is = [&](int nx, int nu) { return d.nx == nx && d.nu == nu; };
-    // big-block family: the shooting grids (explicit integrators) or the collocation grids (the four formulas); with a fixed dt the stage / chain
-    // kernels, with a free dt (...VariableGrid) the sweep kernel's stored Jacobian and the band factorisation (corbo_hip_create, band_route)
     const bool big_grid = (d.defect == CORBO_HIP_DEFECT_RK4_SHOOTING && (d.grid == CORBO_HIP_GRID_MS || d.grid == CORBO_HIP_GRID_MS_VARIABLE)) ||
                           (d.defect != CORBO_HIP_DEFECT_RK4_SHOOTING && (d.grid == CORBO_HIP_GRID_FD || d.grid == CORBO_HIP_GRID_FD_VARIABLE));
-#if __has_include("models/_registry.inc")
-#define CORBO_HIP_USER_MODEL(NAME, SLOT, NX_, NU_, P0, P1, P2, P3) \
-    if (d.dynamics == CORBO_HIP_DYN_USER + SLOT)                     \
-        return is(NX_, NU_) && (NX_ <= 4 || (big_family_dims(NX_, NU_) && big_grid));   // (big-block family: as the quadrotor)
-#include "models/_registry.inc"
-#undef CORBO_HIP_USER_MODEL
-#endif
-    switch (d.dynamics) {
-        case CORBO_HIP_DYN_VAN_DER_POL: case CORBO_HIP_DYN_DUFFING: case CORBO_HIP_DYN_SIMPLE_PENDULUM: case CORBO_HIP_DYN_MASSLESS_PENDULUM:
-        case CORBO_HIP_DYN_TOY_EXAMPLE: case CORBO_HIP_DYN_ARTSTEINS_CIRCLE: return is(2, 1);
-        case CORBO_HIP_DYN_FREE_SPACE_ROCKET: return is(3, 1);
-        case CORBO_HIP_DYN_CART_POLE: return is(4, 1);
-        case CORBO_HIP_DYN_SERIAL_INTEGRATOR: return is(2, 1) || is(3, 1);
-        case CORBO_HIP_DYN_PARALLEL_INTEGRATOR: return is(2, 2) || is(3, 3);
-        case CORBO_HIP_DYN_UNICYCLE: return is(3, 2);
-        case CORBO_HIP_DYN_LINEAR_STATE_SPACE: return is(2, 1) || is(2, 2) || is(3, 1) || is(3, 2) || is(3, 3) || is(4, 1);
-        case CORBO_HIP_DYN_QUADROTOR:   // big-block family: multiple shooting with RK4, fixed dt
-            return is(12, 4) && big_grid;
-        default: return false;
-    }
+    return find_model(d) && known_defect && (d.nx <= 4 || (big_family_dims(d.nx, d.nu) && big_grid));
 }
 
 bool launch_sweep(const corbo_hip_problem_desc& d, const SweepParams& p, hipStream_t stream)
 {
-#if __has_include("models/_registry.inc")
-#define CORBO_HIP_USER_MODEL(NAME, SLOT, NX_, NU_, P0, P1, P2, P3) if (d.dynamics == CORBO_HIP_DYN_USER + SLOT) return sweep_entry_user_##NAME(d.defect, p, stream);
-#include "models/_registry.inc"
-#undef CORBO_HIP_USER_MODEL
-#endif
-    switch (d.dynamics) {
-        case CORBO_HIP_DYN_VAN_DER_POL: return sweep_entry_vdp(d.defect, p, stream);
-        case CORBO_HIP_DYN_SERIAL_INTEGRATOR:
-            if (d.nx == 3) return sweep_entry_integ3(d.defect, p, stream);
-            if (d.nx != 2) return false;
-            return sweep_entry_integ2(d.defect, p, stream);
-        case CORBO_HIP_DYN_UNICYCLE: return sweep_entry_unicycle(d.defect, p, stream);
-        case CORBO_HIP_DYN_QUADROTOR: return sweep_entry_quadrotor(d.defect, p, stream);
-        case CORBO_HIP_DYN_DUFFING: return sweep_entry_duffing(d.defect, p, stream);
-        case CORBO_HIP_DYN_FREE_SPACE_ROCKET: return sweep_entry_rocket(d.defect, p, stream);
-        case CORBO_HIP_DYN_SIMPLE_PENDULUM: return sweep_entry_pendulum(d.defect, p, stream);
-        case CORBO_HIP_DYN_MASSLESS_PENDULUM: return sweep_entry_mpendulum(d.defect, p, stream);
-        case CORBO_HIP_DYN_TOY_EXAMPLE: return sweep_entry_toy(d.defect, p, stream);
-        case CORBO_HIP_DYN_ARTSTEINS_CIRCLE: return sweep_entry_artstein(d.defect, p, stream);
-        case CORBO_HIP_DYN_CART_POLE: return sweep_entry_cartpole(d.defect, p, stream);
-        case CORBO_HIP_DYN_PARALLEL_INTEGRATOR: return d.nx == 2 ? sweep_entry_par2(d.defect, p, stream) : sweep_entry_par3(d.defect, p, stream);
-        case CORBO_HIP_DYN_LINEAR_STATE_SPACE:
-            if (d.nx == 2 && d.nu == 1) return sweep_entry_lin21(d.defect, p, stream);
-            if (d.nx == 2 && d.nu == 2) return sweep_entry_lin22(d.defect, p, stream);
-            if (d.nx == 3 && d.nu == 1) return sweep_entry_lin31(d.defect, p, stream);
-            if (d.nx == 3 && d.nu == 2) return sweep_entry_lin32(d.defect, p, stream);
-            if (d.nx == 3 && d.nu == 3) return sweep_entry_lin33(d.defect, p, stream);
-            if (d.nx == 4 && d.nu == 1) return sweep_entry_lin41(d.defect, p, stream);
-            return false;
-        default: return false;
-    }
+    const ModelEntries* m = find_model(d);
+    return m && m->sweep(d.defect, p, stream);
 }
 
 bool launch_hessian(const corbo_hip_problem_desc& d, const SweepParams& p, const HessParams& hp, hipStream_t stream)
 {
-#if __has_include("models/_registry.inc")
-#define CORBO_HIP_USER_MODEL(NAME, SLOT, NX_, NU_, P0, P1, P2, P3) if (d.dynamics == CORBO_HIP_DYN_USER + SLOT) return hessian_entry_user_##NAME(d.defect, p, hp, stream);
-#include "models/_registry.inc"
-#undef CORBO_HIP_USER_MODEL
-#endif
-    switch (d.dynamics) {
-        case CORBO_HIP_DYN_VAN_DER_POL: return hessian_entry_vdp(d.defect, p, hp, stream);
-        case CORBO_HIP_DYN_SERIAL_INTEGRATOR:
-            if (d.nx == 3) return hessian_entry_integ3(d.defect, p, hp, stream);
-            if (d.nx != 2) return false;
-            return hessian_entry_integ2(d.defect, p, hp, stream);
-        case CORBO_HIP_DYN_UNICYCLE: return hessian_entry_unicycle(d.defect, p, hp, stream);
-        case CORBO_HIP_DYN_QUADROTOR: return hessian_entry_quadrotor(d.defect, p, hp, stream);
-        case CORBO_HIP_DYN_DUFFING: return hessian_entry_duffing(d.defect, p, hp, stream);
-        case CORBO_HIP_DYN_FREE_SPACE_ROCKET: return hessian_entry_rocket(d.defect, p, hp, stream);
-        case CORBO_HIP_DYN_SIMPLE_PENDULUM: return hessian_entry_pendulum(d.defect, p, hp, stream);
-        case CORBO_HIP_DYN_MASSLESS_PENDULUM: return hessian_entry_mpendulum(d.defect, p, hp, stream);
-        case CORBO_HIP_DYN_TOY_EXAMPLE: return hessian_entry_toy(d.defect, p, hp, stream);
-        case CORBO_HIP_DYN_ARTSTEINS_CIRCLE: return hessian_entry_artstein(d.defect, p, hp, stream);
-        case CORBO_HIP_DYN_CART_POLE: return hessian_entry_cartpole(d.defect, p, hp, stream);
-        case CORBO_HIP_DYN_PARALLEL_INTEGRATOR: return d.nx == 2 ? hessian_entry_par2(d.defect, p, hp, stream) : hessian_entry_par3(d.defect, p, hp, stream);
-        case CORBO_HIP_DYN_LINEAR_STATE_SPACE:
-            if (d.nx == 2 && d.nu == 1) return hessian_entry_lin21(d.defect, p, hp, stream);
-            if (d.nx == 2 && d.nu == 2) return hessian_entry_lin22(d.defect, p, hp, stream);
-            if (d.nx == 3 && d.nu == 1) return hessian_entry_lin31(d.defect, p, hp, stream);
-            if (d.nx == 3 && d.nu == 2) return hessian_entry_lin32(d.defect, p, hp, stream);
-            if (d.nx == 3 && d.nu == 3) return hessian_entry_lin33(d.defect, p, hp, stream);
-            if (d.nx == 4 && d.nu == 1) return hessian_entry_lin41(d.defect, p, hp, stream);
-            return false;
-        default: return false;
-    }
+    const ModelEntries* m = find_model(d);
+    return m && m->hessian(d.defect, p, hp, stream);
 }
 
 bool launch_stage_jacobian_dump(const corbo_hip_problem_desc& d, const FactorParams& fp, const SweepParams& sp, double* jac_out, hipStream_t stream)
 {
-    if (!big_family_dims(d.nx, d.nu)) return false;
-    if (d.dynamics == CORBO_HIP_DYN_QUADROTOR) return stage_entry_quadrotor(fp, sp, 0, jac_out, stream);
-#if __has_include("models/_registry.inc")
-#define CORBO_HIP_USER_MODEL(NAME, SLOT, NX_, NU_, P0, P1, P2, P3) if (d.dynamics == CORBO_HIP_DYN_USER + SLOT) return stage_entry_user_##NAME(fp, sp, 0, jac_out, stream);
-#include "models/_registry.inc"
-#undef CORBO_HIP_USER_MODEL
-#endif
-    return false;
+    const ModelEntries* m = find_model(d);   // (small-block models: no stage kernel, the entry returns false)
+    return m && m->stage(fp, sp, 0, jac_out, stream);
 }
 
 bool launch_pass(const corbo_hip_problem_desc& d, const FactorParams& fp, const SweepParams& sp, hipStream_t stream)
 {
-#if __has_include("models/_registry.inc")
-#define CORBO_HIP_USER_MODEL(NAME, SLOT, NX_, NU_, P0, P1, P2, P3) if (d.dynamics == CORBO_HIP_DYN_USER + SLOT) return pass_entry_user_##NAME(d.defect, fp, sp, stream);
-#include "models/_registry.inc"
-#undef CORBO_HIP_USER_MODEL
-#endif
-    switch (d.dynamics) {
-        case CORBO_HIP_DYN_VAN_DER_POL: return pass_entry_vdp(d.defect, fp, sp, stream);
-        case CORBO_HIP_DYN_SERIAL_INTEGRATOR:
-            if (d.nx == 3) return pass_entry_integ3(d.defect, fp, sp, stream);
-            if (d.nx != 2) return false;
-            return pass_entry_integ2(d.defect, fp, sp, stream);
-        case CORBO_HIP_DYN_UNICYCLE: return pass_entry_unicycle(d.defect, fp, sp, stream);
-        case CORBO_HIP_DYN_DUFFING: return pass_entry_duffing(d.defect, fp, sp, stream);
-        case CORBO_HIP_DYN_FREE_SPACE_ROCKET: return pass_entry_rocket(d.defect, fp, sp, stream);
-        case CORBO_HIP_DYN_SIMPLE_PENDULUM: return pass_entry_pendulum(d.defect, fp, sp, stream);
-        case CORBO_HIP_DYN_MASSLESS_PENDULUM: return pass_entry_mpendulum(d.defect, fp, sp, stream);
-        case CORBO_HIP_DYN_TOY_EXAMPLE: return pass_entry_toy(d.defect, fp, sp, stream);
-        case CORBO_HIP_DYN_ARTSTEINS_CIRCLE: return pass_entry_artstein(d.defect, fp, sp, stream);
-        case CORBO_HIP_DYN_CART_POLE: return pass_entry_cartpole(d.defect, fp, sp, stream);
-        case CORBO_HIP_DYN_PARALLEL_INTEGRATOR: return d.nx == 2 ? pass_entry_par2(d.defect, fp, sp, stream) : pass_entry_par3(d.defect, fp, sp, stream);
-        case CORBO_HIP_DYN_LINEAR_STATE_SPACE:
-            if (d.nx == 2 && d.nu == 1) return pass_entry_lin21(d.defect, fp, sp, stream);
-            if (d.nx == 2 && d.nu == 2) return pass_entry_lin22(d.defect, fp, sp, stream);
-            if (d.nx == 3 && d.nu == 1) return pass_entry_lin31(d.defect, fp, sp, stream);
-            if (d.nx == 3 && d.nu == 2) return pass_entry_lin32(d.defect, fp, sp, stream);
-            if (d.nx == 3 && d.nu == 3) return pass_entry_lin33(d.defect, fp, sp, stream);
-            if (d.nx == 4 && d.nu == 1) return pass_entry_lin41(d.defect, fp, sp, stream);
-            return false;
-        default: return false;
-    }
+    const ModelEntries* m = find_model(d);   // (big-block models: no fused pass kernel, the entry returns false)
+    return m && m->pass(d.defect, fp, sp, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -7138,9 +6976,7 @@ bool band_route_supported(int nb, int bw) { return bw + 1 <= 64 && sizeof(double
 bool launch_band_factor(const FactorParams& fp, const BandParams& bp, hipStream_t stream)
 {
     const size_t lds = sizeof(double) * (band_lds_doubles(bp.nb, bp.bw) + 8);   // window + rhs + border + scratch (a horizon of 256 twelve-state intervals: 85 KB)
-    static unsigned long long attr_set = 0;   // (per device)
-    constexpr size_t LDS_MAX = BAND_LDS_MAX;
-    if (first_on_device(attr_set)) { if (hipFuncSetAttribute(reinterpret_cast<const void*>(band_factor_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX) != hipSuccess) (void)hipGetLastError(); }
+    set_max_dynamic_lds(band_factor_kernel, (int)BAND_LDS_MAX);
     if (!bp.work || !band_route_supported(bp.nb, bp.bw)) return false;
     {
         // list entries per thread: an entry is a chain of dependent loads (index, pair, two values).  Small batches are latency-bound -- two per thread (one OCP:
@@ -7154,13 +6990,9 @@ bool launch_band_factor(const FactorParams& fp, const BandParams& bp, hipStream_
     // half-bandwidth <= 7: one wave per instance, window in registers (band_narrow_kernel); option "band_wide" keeps the eight-wave kernel (A/B, tests)
     const size_t lds_n = sizeof(double) * (2 * (size_t)bp.nb + 8);
     if (bp.bw <= 7 && !fp.band_wide && lds_n <= BAND_LDS_MAX) {
-        static unsigned long long attr_n = 0;   // (per device)
-        if (first_on_device(attr_n)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(band_narrow_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX) != hipSuccess) (void)hipGetLastError();
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(band_narrow_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX) != hipSuccess) (void)hipGetLastError();
-        }
-        if (bp.nb < bp.n) hipLaunchKernelGGL(band_narrow_kernel<true>, dim3(fp.batch), dim3(64), lds_n, stream, fp, bp);
-        else hipLaunchKernelGGL(band_narrow_kernel<false>, dim3(fp.batch), dim3(64), lds_n, stream, fp, bp);
+        const auto narrow = (bp.nb < bp.n) ? band_narrow_kernel<true> : band_narrow_kernel<false>;
+        set_max_dynamic_lds(narrow, (int)BAND_LDS_MAX);
+        hipLaunchKernelGGL(narrow, dim3(fp.batch), dim3(64), lds_n, stream, fp, bp);
         return true;
     }
     hipLaunchKernelGGL(band_factor_kernel, dim3(fp.batch), dim3(512), lds, stream, fp, bp);
@@ -7178,22 +7010,10 @@ size_t big_stage_cache_doubles(const corbo_hip_problem_desc& d, int N)
 bool launch_factor(const corbo_hip_problem_desc& d, const FactorParams& p, hipStream_t stream, const SweepParams* sp)
 {
     if (big_family_dims(d.nx, d.nu)) {   // big-block family: the model's own unit
-        if (!sp) return false;
-        if (d.dynamics == CORBO_HIP_DYN_QUADROTOR) return factor_entry_quadrotor(p, *sp, stream);
-#if __has_include("models/_registry.inc")
-#define CORBO_HIP_USER_MODEL(NAME, SLOT, NX_, NU_, P0, P1, P2, P3) if (d.dynamics == CORBO_HIP_DYN_USER + SLOT) return factor_entry_user_##NAME(p, *sp, stream);
-#include "models/_registry.inc"
-#undef CORBO_HIP_USER_MODEL
-#endif
-        return false;
+        const ModelEntries* m = find_model(d);
+        return sp && m && m->factor(p, *sp, stream);
     }
-    if (d.nx == 2 && d.nu == 1) return launch_factor_t<2, 1>(p, stream);
-    if (d.nx == 3 && d.nu == 2) return launch_factor_t<3, 2>(p, stream);
-    if (d.nx == 3 && d.nu == 1) return launch_factor_t<3, 1>(p, stream);
-    if (d.nx == 4 && d.nu == 1) return launch_factor_t<4, 1>(p, stream);
-    if (d.nx == 2 && d.nu == 2) return launch_factor_t<2, 2>(p, stream);
-    if (d.nx == 3 && d.nu == 3) return launch_factor_t<3, 3>(p, stream);
-    return false;
+    return with_small_shape(d.nx, d.nu, false, [&](auto nx, auto nu) { return launch_factor_t<decltype(nx)::value, decltype(nu)::value>(p, stream); });
 }
 
 #endif  // !CORBO_HIP_DYN_TU

@@ -296,7 +296,7 @@ void launch_upload_instance(const UploadParams& p, hipStream_t stream);
 // every interval) at the accepted iterate, written into jac_out [batch][nnz_pad] in the public value order; needs a residual sweep
 // (mode 0 / 1 with sp.xe0) of the same iterate before it
 bool launch_stage_jacobian_dump(const corbo_hip_problem_desc& d, const FactorParams& fp, const SweepParams& sp, double* jac_out, hipStream_t stream);
-bool device_kernels_exist(const corbo_hip_problem_desc& d);   // host-only mirror of the dispatch (corbo_hip_create's gate)
+bool device_kernels_exist(const corbo_hip_problem_desc& d);   // host-only: the dispatch has kernels for d (corbo_hip_create's gate)
 bool launch_pass(const corbo_hip_problem_desc& d, const FactorParams& fp, const SweepParams& sp, hipStream_t stream);
 bool launch_band_factor(const FactorParams& fp, const BandParams& bp, hipStream_t stream);
 // Block-tridiagonal route (lm_bt_kernel): what corbo_hip_create asks before it builds the tables -- block size s = nx + nu, free dt, grid points, the
