@@ -169,6 +169,26 @@ struct corbo_hip_solver {
     // corbo_hip_solve_async: solves enqueued and not yet waited for (their timing event pairs; the pass-limit flag alternates between two pinned slots)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> async_events, event_pool;
     int async_pending = 0;
+    // Two lanes (round 7): everything ONE launch of the run-to-completion kernel writes exists twice -- a stream, the device working set, the per-CU
+    // progress table, the pinned sink pair -- so that back-to-back re-arming solves (new_run = 2: they start from the shared shadow copy d_x0 and do
+    // not depend on each other) alternate between the lanes and share the chip: the workgroups of step k + 1 fill the slots that step k's finished
+    // instances free while its stragglers still run.  The handle's own fields (stream, d_x, ..., h_stage, h_state) ARE the current lane, the one
+    // that holds the newest solve; `idle` holds the other set and route_to_other_lane() swaps the two, so every other entry point keeps reading the
+    // handle's fields.  The second set is allocated by the first solve that can use it (a handle that never streams pays nothing).
+    struct Lane {
+        hipStream_t stream = nullptr;
+        double *d_x = nullptr, *d_xt = nullptr, *d_values0 = nullptr, *d_values1 = nullptr, *d_jac = nullptr, *d_chi2 = nullptr, *d_bt_snap = nullptr;
+        LmState* d_state = nullptr;
+        int32_t* d_queue = nullptr;
+        double* h_stage = nullptr;
+        LmState* h_state = nullptr;
+    } idle;
+    bool lane_b_ready = false;   // `idle` is allocated
+    int cur_lane      = 0;       // which set the handle's fields hold (0 = the one corbo_hip_create allocated)
+    int async_lanes   = 2;       // corbo_hip_set_option("async_lanes"): 1 = every solve on the one stream, as before round 7 (A/B)
+    bool idle_busy    = false;   // the idle lane has work in flight that nothing on the current lane's stream is ordered behind yet
+    hipEvent_t ev_join = nullptr;
+    std::vector<int> async_event_lane;   // lane of every entry of async_events (corbo_hip_get_timing: the union of the launches' intervals)
     int m_pad = 0, nnz_pad = 0;
     int jlean_lo2 = 0, jlean_hi2 = 0;   // kernels.hpp SweepParams::jlean_*
     // Hessian-path operators: the structure of a (handle, lower) pair is built once, scratch buffers only grow (an interior-point
@@ -714,6 +734,15 @@ void corbo_hip_destroy(corbo_hip_handle h)
     if (!h) return;
     DeviceGuard device_guard(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
+    if (h->idle.stream) { (void)hipStreamSynchronize(h->idle.stream); (void)hipStreamDestroy(h->idle.stream); }
+    {
+        const corbo_hip_solver::Lane& l = h->idle;
+        void* lane_ptrs[] = {l.d_x, l.d_xt, l.d_values0, l.d_values1, l.d_jac, l.d_chi2, l.d_bt_snap, l.d_state, l.d_queue};
+        for (void* p : lane_ptrs) if (p) (void)hipFree(p);
+        if (l.h_stage) (void)hipHostFree(l.h_stage);
+        if (l.h_state) (void)hipHostFree(l.h_state);
+        if (h->ev_join) (void)hipEventDestroy(h->ev_join);
+    }
     void* ptrs[] = {h->d_stage_cols, h->d_comp, h->d_ineq_cols, h->d_ineq_rows,
                     h->d_x0, h->d_x, h->d_xt, h->d_lb, h->d_ub, h->d_xref, h->d_values0, h->d_values1, h->d_jac, h->d_state, h->d_chi2, h->d_work, h->d_xe0, h->d_counters, h->d_queue, h->d_bound_rows, h->d_xplant, h->d_loop, h->d_lin, h->d_wdense, h->d_refvec, h->d_reftraj, h->d_plant_prm, h->d_dyn_inst,
                     h->d_xedges, h->d_xparams, h->d_uprev, h->d_band_work, h->d_band_target, h->d_band_ptr, h->d_band_pairs, h->d_band_rptr, h->d_band_rent, h->d_band_voff,
@@ -910,6 +939,71 @@ static int deliver_results(corbo_hip_handle h)
     return CORBO_HIP_OK;
 }
 
+// ---- the two lanes of a handle (corbo_hip_solver::Lane)
+static void swap_lanes(corbo_hip_handle h)
+{
+    corbo_hip_solver::Lane& l = h->idle;
+    std::swap(h->stream, l.stream);
+    std::swap(h->d_x, l.d_x); std::swap(h->d_xt, l.d_xt); std::swap(h->d_values0, l.d_values0); std::swap(h->d_values1, l.d_values1);
+    std::swap(h->d_jac, l.d_jac); std::swap(h->d_chi2, l.d_chi2); std::swap(h->d_bt_snap, l.d_bt_snap); std::swap(h->d_state, l.d_state);
+    std::swap(h->d_queue, l.d_queue); std::swap(h->h_stage, l.h_stage); std::swap(h->h_state, l.h_state);
+    h->cur_lane ^= 1;
+}
+
+// the second set: sizes and initial contents as corbo_hip_create gives the first one (handles with a run-to-completion kernel: no spare rows, no
+// factor workspace in HBM); the clears run on the new lane's own stream, in front of its first launch
+static int create_second_lane(corbo_hip_handle h)
+{
+    corbo_hip_solver::Lane& l = h->idle;
+    const Structure& S = h->S;
+    const size_t B = (size_t)h->batch + (size_t)h->spare;
+    const size_t queue_ints = (size_t)(16 + 2048 * 16);
+    auto build = [&]() -> int {
+        // (created while the first lane's stream has a launch in flight: the runtime hands a new stream the least used of its hardware queues, i.e. not
+        //  the one that launch occupies -- docs/measurements/r07.md quotes the overlap from a kernel trace)
+        HIP_TRY(hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
+        struct { double** p; size_t n; } dev[] = {{&l.d_x, B * S.nvs}, {&l.d_xt, B * S.nvs}, {&l.d_values0, B * h->m_pad}, {&l.d_values1, B * h->m_pad},
+                                                 {&l.d_jac, (size_t)h->batch * h->nnz_pad}, {&l.d_chi2, B},
+                                                 {&l.d_bt_snap, h->d_bt_snap ? (size_t)h->batch * (size_t)h->bt_snap_stride : 0}};
+        for (auto& d : dev) {
+            if (!d.n) continue;
+            HIP_TRY(hipMalloc((void**)d.p, d.n * sizeof(double)));
+            if (d.p != &l.d_bt_snap) HIP_TRY(hipMemsetAsync(*d.p, 0, d.n * sizeof(double), l.stream));
+        }
+        HIP_TRY(hipMalloc((void**)&l.d_state, B * sizeof(LmState)));
+        HIP_TRY(hipMemsetAsync(l.d_state, 0, B * sizeof(LmState), l.stream));
+        HIP_TRY(hipMalloc((void**)&l.d_queue, queue_ints * sizeof(int32_t)));
+        HIP_TRY(hipMemsetAsync(l.d_queue, 0, queue_ints * sizeof(int32_t), l.stream));
+        HIP_TRY(hipHostMalloc((void**)&l.h_stage, (size_t)h->batch * (size_t)(S.nvs > CORBO_HIP_MAX_NX ? S.nvs : CORBO_HIP_MAX_NX) * sizeof(double)));
+        HIP_TRY(hipHostMalloc((void**)&l.h_state, (size_t)h->batch * sizeof(LmState)));
+        return CORBO_HIP_OK;
+    };
+    const int rc = build();
+    if (rc) {   // nothing half-built stays behind: the next solve tries again
+        if (l.stream) { (void)hipStreamSynchronize(l.stream); (void)hipStreamDestroy(l.stream); }
+        void* ptrs[] = {l.d_x, l.d_xt, l.d_values0, l.d_values1, l.d_jac, l.d_chi2, l.d_bt_snap, l.d_state, l.d_queue};
+        for (void* p : ptrs) if (p) (void)hipFree(p);
+        if (l.h_stage) (void)hipHostFree(l.h_stage);
+        if (l.h_state) (void)hipHostFree(l.h_state);
+        if (h->ev_join) { (void)hipEventDestroy(h->ev_join); h->ev_join = nullptr; }
+        l = corbo_hip_solver::Lane{};
+        return rc;
+    }
+    h->lane_b_ready = true;
+    return CORBO_HIP_OK;
+}
+
+// whatever is enqueued on the current lane's stream from here on runs behind the idle lane's launches as well (no host wait)
+static int join_lanes(corbo_hip_handle h)
+{
+    if (!h->idle_busy) return CORBO_HIP_OK;
+    HIP_TRY(hipEventRecord(h->ev_join, h->idle.stream));
+    HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));
+    h->idle_busy = false;
+    return CORBO_HIP_OK;
+}
+
 static int finish_async(corbo_hip_handle h, bool report)
 {
     auto deferred = [&]() -> int {
@@ -919,12 +1013,43 @@ static int finish_async(corbo_hip_handle h, bool report)
     };
     if (h->async_pending == 0) return deferred();
     HIP_TRY(hipStreamSynchronize(h->stream));
-    for (auto& pr : h->async_events) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) { h->solve_ms_sum += ms; h->stats.solve_ms = ms; }
-        h->event_pool.push_back(pr);
+    if (h->lane_b_ready) HIP_TRY(hipStreamSynchronize(h->idle.stream));
+    h->idle_busy = false;
+    // The launches of the two lanes overlap: the handle's time is the length of the UNION of their intervals.  In completion order (a lane's launches
+    // complete in the order they were enqueued; the heads of the two lanes are compared by their end events) launch k is charged
+    // end_k - max(start_k, end_{k-1}).  A predecessor on the same stream ended before start_k: the charge is the launch's own interval, as on one lane.
+    {
+        const size_t n = h->async_events.size();
+        size_t head[2] = {0, 0};
+        auto advance = [&](int lane) { while (head[lane] < n && h->async_event_lane[head[lane]] != lane) ++head[lane]; };
+        advance(0); advance(1);
+        hipEvent_t prev_end = nullptr;
+        int prev_lane = -1;
+        while (head[0] < n || head[1] < n) {
+            int lane = head[0] < n ? 0 : 1;
+            if (head[0] < n && head[1] < n) {
+                float d = 0;   // end of lane 1's head minus end of lane 0's head
+                if (hipEventElapsedTime(&d, h->async_events[head[0]].second, h->async_events[head[1]].second) == hipSuccess && d < 0) lane = 1;
+            }
+            const auto& pr = h->async_events[head[lane]];
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) {
+                float gap = ms;
+                if (prev_end && prev_lane != lane && hipEventElapsedTime(&gap, prev_end, pr.second) != hipSuccess) gap = ms;
+                if (gap < 0) gap = 0;
+                h->solve_ms_sum += (gap < ms ? gap : ms);
+            }
+            prev_end = pr.second; prev_lane = lane;
+            ++head[lane]; advance(lane);
+        }
+        if (n) {   // corbo_hip_stats::solve_ms: the newest solve's own interval
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, h->async_events[n - 1].first, h->async_events[n - 1].second) == hipSuccess) h->stats.solve_ms = ms;
+        }
+        for (auto& pr : h->async_events) h->event_pool.push_back(pr);
     }
     h->async_events.clear();
+    h->async_event_lane.clear();
     h->async_pending = 0;
     const bool unfinished = h->h_counter[0] != 0 || h->h_counter[1] != 0;
     h->h_counter[0] = h->h_counter[1] = 0;
@@ -982,6 +1107,19 @@ static int solve_impl(corbo_hip_handle h, const corbo_hip_lm_opts* o, int new_ru
     const bool run_to_completion = !split && h->loop_mode && o->iterations > 0;
     if (rearm && !run_to_completion) { launch_copy_rows(h->d_x0, h->d_x, nullptr, (size_t)h->batch * h->S.nvs, h->stream); HIP_TRY(hipGetLastError()); }
     if (async && !run_to_completion) { const int rc0 = finish_async(h); if (rc0) return rc0; async = false; }   // (host-driven passes: synchronous)
+    // Lanes: an enqueued re-arming solve behind a solve that is still in flight takes the OTHER lane and does not wait for it (it starts from d_x0, not
+    // from that solve's result), unless the launch would be in queue mode or a diagnostic that owns per-handle buffers is on.  Every other enqueued solve
+    // continues from the newest iterate: it stays on the current lane, ordered behind both.  (A synchronous solve has drained both lanes already.)
+    if (async) {
+        const bool other_lane = rearm && h->async_lanes == 2 && h->async_pending > 0 && !(h->active > 4 * h->num_cus) && !h->profile && !h->phase_cycles &&
+                                h->pass_timeline_inst < 0 && !h->sweep_timeline && !h->d_work && !h->d_xe0;
+        if (other_lane) {
+            if (!h->lane_b_ready) { const int rc_l = create_second_lane(h); if (rc_l) return rc_l; }
+            swap_lanes(h);
+            h->idle_busy = true;   // (the lane just left holds the solve in flight; this lane's earlier launches are ahead on its own stream)
+        }
+        else { const int rc_j = join_lanes(h); if (rc_j) return rc_j; }
+    }
     // (measured and not kept: asynchronous run-to-completion solves delivering through the copy engine as well -- the kernel alone is 7.5 us shorter
     //  without its own stores into pinned host memory, but the cross-stream waits and the engine's traffic cost more: 0.543 -> 0.753 ms per step)
     std::pair<hipEvent_t, hipEvent_t> aev{nullptr, nullptr};
@@ -1192,7 +1330,7 @@ static int solve_impl(corbo_hip_handle h, const corbo_hip_lm_opts* o, int new_ru
             HIP_TRY(hipStreamWaitEvent(h->stream, h->sub_done[i], 0));
         }
     if (async) {   // no wait: finish_async does the rest
-        if (aev.first) { HIP_TRY(hipEventRecord(aev.second, h->stream)); h->async_events.push_back(aev); }
+        if (aev.first) { HIP_TRY(hipEventRecord(aev.second, h->stream)); h->async_events.push_back(aev); h->async_event_lane.push_back(h->cur_lane); }
         h->async_pending += 1;
         h->solve_count += 1;
         h->stats.passes = 1;
@@ -1305,6 +1443,7 @@ int corbo_hip_restore_instance_data(corbo_hip_handle h)
     //  solves must not come back as "valid" when they are drained -- the device iterates are the re-armed ones by then)
     h->sink_valid = false;   // the pinned result views are stale from here on
     h->sink_invalidated = true;
+    { const int rc_j = join_lanes(h); if (rc_j) return rc_j; }   // (the newest lane's iterate is the handle's iterate; what follows on its stream is behind both lanes)
     launch_copy_rows(h->d_x0, h->d_x, nullptr, (size_t)h->batch * h->S.nvs, h->stream);
     HIP_TRY(hipGetLastError());
     return CORBO_HIP_OK;
@@ -1663,6 +1802,10 @@ int corbo_hip_set_option(corbo_hip_handle h, const char* name, int value)
     else if (n == "phase_cycles") h->phase_cycles = value != 0;
     else if (n == "ff_converged") h->ff_converged = value;
     else if (n == "solve_timing") h->solve_timing = value;
+    else if (n == "async_lanes") {
+        if (value != 1 && value != 2) return fail(CORBO_HIP_ERR_INVALID, "async_lanes: 1 or 2");
+        h->async_lanes = value;
+    }
     else return fail(CORBO_HIP_ERR_INVALID, "unknown option: " + n);
     return CORBO_HIP_OK;
 }
@@ -2136,6 +2279,11 @@ ABI_CATCH
 int corbo_hip_device_views(corbo_hip_handle h, double** x_dev, double** chi2_dev, void** hip_stream)
 {
     if (!h) return fail(CORBO_HIP_ERR_INVALID, "null handle");
+    if (h->idle_busy) {   // the views are the newest lane's; its stream is ordered behind the other lane's launches first
+        ON_DEVICE_OF(h);
+        const int rc_j = join_lanes(h);
+        if (rc_j) return rc_j;
+    }
     if (x_dev) *x_dev = h->d_x;
     if (chi2_dev) *chi2_dev = h->d_chi2;
     if (hip_stream) *hip_stream = (void*)h->stream;

@@ -488,7 +488,20 @@ int corbo_hip_solve(corbo_hip_handle h, const corbo_hip_lm_opts* opts, int new_r
  * and the pass-limit check of the enqueued solves become available with the next corbo_hip_synchronize / corbo_hip_solve / corbo_hip_get_* /
  * corbo_hip_fetch_solution call (an error of an enqueued solve is reported there).  Entry points that CHANGE the handle's data (set_instance_data,
  * warm_start, set_references ...) wait for the enqueued solves and then do their work; they never return an enqueued solve's error -- it stays pending
- * for the next of the calls named above. */
+ * for the next of the calls named above.
+ * Two lanes (round 7).  A handle keeps everything one launch writes -- stream, device working set, pinned result buffers -- twice; the second set is
+ * allocated by the first solve that uses it.  An enqueued re-arming solve (new_run = 2) that finds another solve of the handle still in flight takes the
+ * lane that solve is NOT on and does not wait for it: it starts from the uploaded iterates, not from that solve's result, so the two launches share the
+ * chip (the younger one's workgroups fill the slots the older one's finished instances free).  Conditions: a run-to-completion handle, a batch of at
+ * most 4 workgroups per compute unit (larger batches run through the instance queue and fill the chip on their own), none of the diagnostics "profile",
+ * "phase_cycles", "pass_timeline", "sweep_timeline".  Every other call -- corbo_hip_solve, new_run = 0 / 1 (they continue from the newest iterate),
+ * corbo_hip_restore_instance_data, corbo_hip_device_views, every getter and mutator -- is ordered behind BOTH lanes and works on the lane of the newest
+ * solve: results, statistics and views are always those of the solve enqueued last.  Consequences for a caller: the pinned views of
+ * corbo_hip_fetch_solution and the pointers of corbo_hip_device_views belong to the newest lane, so ask for them again after enqueuing re-arming solves
+ * instead of caching them across such calls; with the result sink on, the previous step's pinned results are no longer overwritten while the next step runs.
+ * The block-tridiagonal route's handles use both lanes as well (their snapshot buffer exists per lane).  corbo_hip_set_option(h, "async_lanes", 1) keeps
+ * every solve on one stream as before.  corbo_hip_stats::solve_ms of an enqueued solve is its own launch interval; under overlap it is longer than the
+ * same launch alone, and corbo_hip_get_timing does not add such intervals up (see there). */
 int corbo_hip_solve_async(corbo_hip_handle h, const corbo_hip_lm_opts* opts, int new_run);
 
 /* Block until the handle's stream is idle. */
@@ -517,8 +530,11 @@ int corbo_hip_fetch_solution(corbo_hip_handle h, const double** x_pinned, int32_
  * wait for it (smaller batches: corbo_hip_fetch_solution copies, as without the sink). */
 int corbo_hip_set_result_sink(corbo_hip_handle h, int enable);
 
-/* Accumulated HIP-event time [ms] (handle's stream, first launch to last kernel end) and number of corbo_hip_solve calls since the
- * last reset: the average launch duration of the run-to-completion solve kernel, measured live (bench.py roofline object). */
+/* Accumulated HIP-event time [ms] (first launch to last kernel end of every solve) and number of corbo_hip_solve / corbo_hip_solve_async calls since
+ * the last reset: the average launch duration of the run-to-completion solve kernel, measured live (bench.py roofline object).  Enqueued solves on the
+ * two lanes of a handle overlap, so the sum is the length of the UNION of the launch intervals, not the sum of their lengths: in completion order
+ * launch k adds end_k - max(start_k, end_{k-1}).  Launches that do not overlap (one lane, synchronous solves) add their own interval as before; sum / solves
+ * is then the time the chip spent per solve, which is what a per-launch roofline wants -- the average length of an overlapped launch is longer. */
 int corbo_hip_get_timing(corbo_hip_handle h, double* solve_ms_sum, int64_t* solves, int reset);
 
 /* Measurement hook (bench.py `roofline_sweep_phase`, profiles/rNN_pass_phases.json): with corbo_hip_set_option(h, "phase_cycles", 1) the
@@ -583,7 +599,8 @@ int corbo_hip_linear_form_structure(const corbo_hip_problem_desc* desc, int32_t*
 int corbo_hip_eval_linear_form(corbo_hip_handle h, double* vals, double* lbA, double* ubA);
 
 /* Device-resident views for callers that already live on the GPU (torch tensors, RCCL gathers): pointers into
- * the library's HBM buffers, valid until corbo_hip_destroy.  x: [batch][nv], chi2: [batch]. */
+ * the library's HBM buffers, valid until corbo_hip_destroy.  x: [batch][nv], chi2: [batch].  They are the buffers and the stream of the lane that
+ * holds the newest solve (corbo_hip_solve_async): ask again after enqueuing re-arming solves.  The stream handed out is ordered behind both lanes. */
 int corbo_hip_device_views(corbo_hip_handle h, double** x_dev, double** chi2_dev, void** hip_stream);
 /* Row stride (doubles) of the x view: dims.nv values + the library's padding (a fixed dt lives there too). */
 int corbo_hip_device_row_stride(corbo_hip_handle h, int32_t* row_stride);
@@ -624,6 +641,8 @@ int corbo_hip_eval_stage_function(int id, int dim, int n, const double* v, const
  *   "run_to_completion" 0: one launch per LM pass (the host counts unfinished instances) instead of one launch per solve
  *   "pass_timeline"     value >= 0: corbo_hip_solve prints the per-pass shader-clock stamps of instance `value` on stderr; -1: off
  *   "sweep_timeline"    1: corbo_hip_time_sweep prints the phase stamps of instance 0 on stderr
+ *   "async_lanes"       2 (default): enqueued re-arming solves alternate between the handle's two lanes and overlap (corbo_hip_solve_async); 1: one stream
+ *                       for everything, as before round 7 (A/B, tests)
  *   "solve_timing"      0: corbo_hip_solve records no HIP timing events around its launches (corbo_hip_stats::solve_ms and corbo_hip_get_timing stay 0):
  *                       7 - 13 us less per call, what a caller that solves ONE problem per call wants (the drop-in adapter sets it)
  *   "ff_converged"      0: compute the outer iterations that follow a converged step instead of counting them (A/B and tests)
