@@ -258,6 +258,8 @@ struct corbo_hip_solver {
     int pass_timeline_inst = -1;   // corbo_hip_set_option("pass_timeline"): >= 0 prints that instance's per-pass shader-clock stamps
     bool sweep_timeline = false;   // corbo_hip_set_option("sweep_timeline")
     int stagger = 0;               // corbo_hip_set_option("stagger")
+    int plain_kernel = 1;          // corbo_hip_set_option("plain_kernel"): 0 = the general fused pass kernel also where the plain instantiation applies (A/B, tests)
+    bool second_rows = false;      // some component carries a second cost row (terminal equality, duplicated dt edge): never the plain instantiation
     int pass_threads = 0;          // corbo_hip_set_option("pass_threads"): 0 = the default workgroup size of the run-to-completion kernel
     int lag_priority = 1;          // corbo_hip_set_option("lag_priority")
     bool phase_cycles = false;     // corbo_hip_set_option("phase_cycles"): per-instance phase totals (FactorParams::phase_cycles)
@@ -334,6 +336,7 @@ struct corbo_hip_solver {
         p.stage_cache = d_stage_cache; p.stage_cache_stride = (int64_t)stage_cache_stride;
         p.defect = S.desc.defect;
         p.wdense_mask = d_wdense ? S.desc.weights_dense : 0;
+        p.plain_ok = (plain_kernel && !second_rows) ? 1 : 0;
         p.bt_pairs = d_bt_pairs; p.bt_off = d_bt_off; p.bt_target = d_bt_target; p.bt_rounds = bt_rounds; p.bt_snap = d_bt_snap; p.bt_snap_stride = bt_snap_stride; p.bt_waves = bt_waves; p.num_cus = num_cus;
         return p;
     }
@@ -480,6 +483,7 @@ static int create_impl(const corbo_hip_problem_desc* desc, int batch, int device
         for (auto& c : sc) for (int& o : c.col) o = mp(o);
         std::vector<CompInfo> ci = S.comp;
         for (auto& c : ci) { c.cost_joff = mp(c.cost_joff); c.bnd_joff = mp(c.bnd_joff); c.cost2_joff = mp(c.cost2_joff); }
+        for (const auto& c : ci) if (c.cost2_row >= 0 || c.cost2_joff >= 0) h->second_rows = true;
         std::vector<int32_t> ic = S.ineq_cols;
         for (int32_t& o : ic) o = mp(o);
         for (int i = 0; i < CORBO_HIP_MAX_NX; ++i) h->fin_joff_dev[i] = (i < S.nx) ? mp(S.fin_joff[i]) : -1;
@@ -1277,6 +1281,7 @@ static int solve_impl(corbo_hip_handle h, const corbo_hip_lm_opts* o, int new_ru
                 (void)hipFree(p); } } ptl_guard{d_ptl, st_of[i], h->raw_stamps};
             if (!launch_pass(h->S.desc, fp, sp, st_of[i])) return fail(CORBO_HIP_ERR_UNSUPPORTED, "no fused pass kernel for this descriptor");
             HIP_TRY(hipGetLastError());
+            h->stats.plain_kernel = pass_kernel_is_plain(fp, sp) ? 1 : 0;
             pass_of[i] = 1;
         }
     }
@@ -1797,6 +1802,7 @@ int corbo_hip_set_option(corbo_hip_handle h, const char* name, int value)
     else if (n == "reject_speculation") h->reject_speculation = value;
     else if (n == "stagger") h->stagger = value;
     else if (n == "pass_threads") h->pass_threads = value;
+    else if (n == "plain_kernel") h->plain_kernel = value != 0;
     else if (n == "lag_priority") h->lag_priority = value;
     else if (n == "raw_stamps") h->raw_stamps = value != 0;
     else if (n == "phase_cycles") h->phase_cycles = value != 0;

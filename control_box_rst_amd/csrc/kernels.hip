@@ -88,6 +88,10 @@ R with_small_shape(int nx, int nu, R none, F&& f)
 // global stores that nobody in the workgroup is going to read (gfx9 counts stores in vmcnt) -- an HBM / L2 round trip at every
 // barrier that follows a store.  Where the data that crosses the barrier lives in LDS, waiting for the wave's LDS operations is
 // enough.  (-DCORBO_HIP_FULL_BARRIERS: the conservative barrier everywhere, for A/B measurements.)
+// PLAIN instantiations (lm_pass_kernel, sweep_body): an option of the parameter blocks that the plain problem class never turns on reads as its
+// "off" value at compile time -- the field is not loaded and everything behind its test is dead code.  (PLAIN = false: the field itself, nothing changes.)
+#define PLAIN_OFF(field, off) (PLAIN ? decltype(field)(off) : (field))
+
 __device__ __forceinline__ void lds_barrier()
 {
 #ifdef CORBO_HIP_FULL_BARRIERS
@@ -206,7 +210,7 @@ constexpr int SWEEP_ROLE_TABLE = 2 * CORBO_HIP_MAX_NX + CORBO_HIP_MAX_NX + CORBO
 #else
 #define SWEEP_STAMP(id)                                                     \
     do {                                                                    \
-        if (p.timeline && inst == p.timeline_inst && tid == 0) p.timeline[id] = clock64(); \
+        if (PLAIN_OFF(p.timeline, nullptr) && inst == p.timeline_inst && tid == 0) p.timeline[id] = clock64(); \
     } while (0)
 #endif
 
@@ -297,7 +301,9 @@ __device__ __forceinline__ void xedge_values(const XEdge& xe, const double (&loc
 
 // XE: the descriptor has integral-form constraint edges / control-deviation edges (SweepParams::xedges): one lane per such edge evaluates it
 // generically (values before the chi2 reduction, central-difference blocks with the other Jacobian entries).  Stand-alone kernels only.
-template <int DYN, int DEFECT, bool FUSED, bool DENSE = false, bool LONG = false, int THREADS = SWEEP_THREADS, bool XE = false, bool NOJAC = false>
+// PLAIN: the plain problem class of the two-wave fixed-horizon shape (lm_pass_kernel): no stage or final inequality, no terminal equality or second cost row, no
+// per-vertex references, no diagnostics -- those options are compile-time "off" (PLAIN_OFF); every floating-point expression that is left is the general one.
+template <int DYN, int DEFECT, bool FUSED, bool DENSE = false, bool LONG = false, int THREADS = SWEEP_THREADS, bool XE = false, bool NOJAC = false, bool PLAIN = false>
 __device__ __forceinline__ void sweep_body(const SweepParams& p, const int mode, int32_t* const active_count, LmState* const st, double* xs, double* red, double* cs, double* jst, const int inst, const int tid, const bool xs_ready = false,
                                            StageKeep<Dynamics<DYN>::NX, Dynamics<DYN>::NU>* const keep = nullptr, const bool in_loop = false, int* const sc_out = nullptr)
 {
@@ -395,7 +401,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams& p, const int mode,
             reinterpret_cast<double2*>(xs)[i] = reinterpret_cast<const double2*>(xsrc)[i];
     double xr[NX];
 #pragma unroll
-    for (int i = 0; i < NX; ++i) xr[i] = p.refvec ? p.refvec[xo + (size_t)(p.N - 1) * S + i] : p.xref[(size_t)inst * CORBO_HIP_MAX_NX + i];
+    for (int i = 0; i < NX; ++i) xr[i] = PLAIN_OFF(p.refvec, nullptr) ? p.refvec[xo + (size_t)(p.N - 1) * S + i] : p.xref[(size_t)inst * CORBO_HIP_MAX_NX + i];
     // big models (stand-alone kernel): weight and reference of a component by its slot, in LDS in front of the LM state.  Selecting them out of the
     // kernel arguments costs a compare / select chain over NX entries per component, and the 40 scalars it runs over do not fit the scalar
     // register file next to everything else (the compiler parked them in vector-register lanes: 719 v_readlane in the component phase of the
@@ -404,7 +410,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams& p, const int mode,
     double* const role = reinterpret_cast<double*>(st) - SWEEP_ROLE_TABLE;   // [0, S): sqrt(Q_ii) | sqrt(R_jj); [S, S + NX): sqrt(Qf_ii); [S + NX, S + 2 NX): xref
     if constexpr (ROLE_TAB) {
         if (tid < S) role[tid] = (tid < NX) ? p.mp.sq[tid < NX ? tid : 0] : p.mp.sr[tid < NX ? 0 : tid - NX];
-        if (tid < NX) { role[S + tid] = p.mp.sqf[tid]; role[S + NX + tid] = p.refvec ? p.refvec[xo + (size_t)(p.N - 1) * S + tid] : p.xref[(size_t)inst * CORBO_HIP_MAX_NX + tid]; }
+        if (tid < NX) { role[S + tid] = p.mp.sqf[tid]; role[S + NX + tid] = PLAIN_OFF(p.refvec, nullptr) ? p.refvec[xo + (size_t)(p.N - 1) * S + tid] : p.xref[(size_t)inst * CORBO_HIP_MAX_NX + tid]; }
     }
     lds_barrier();
     SWEEP_STAMP(1);
@@ -437,7 +443,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams& p, const int mode,
             if (cls != 1) {
 #pragma unroll
                 for (int i = 0; i < NX; ++i) rj = (j == i) ? xr[i] : rj;
-                if (p.refvec && j < dim) rj = p.refvec[xo + v - c + j];
+                if (PLAIN_OFF(p.refvec, nullptr) && j < dim) rj = p.refvec[xo + v - c + j];
             }
             xd[j] = (j < dim) ? xs[v - c + j] - rj : 0.0;
         }
@@ -471,7 +477,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams& p, const int mode,
         // time-varying state references (ReferenceTrajectoryInterface::getReferenceCached(k), quadratic_cost.cpp:100-119): one per component.
         // (Controls keep the zero reference: the reference's least-squares control term with a non-zero uref is not a function of the
         // control vector -- quadratic_cost.cpp:160-163 assigns the scalar ud^T R^(1/2) ud to the nu-vector.)
-        if (p.refvec && !is_dt && !is_u) ref = p.refvec[xo + v];
+        if (PLAIN_OFF(p.refvec, nullptr) && !is_dt && !is_u) ref = p.refvec[xo + v];
         dim = is_dt ? 1 : (is_u ? NU : NX);
         c   = is_dt ? 0 : (is_u ? cu : cs_);
         fin = is_fin;
@@ -488,7 +494,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams& p, const int mode,
                 if (cls != 1) {
 #pragma unroll
                     for (int i = 0; i < NX; ++i) refc = (c == i) ? xr[i] : refc;
-                    if (p.refvec) refc = p.refvec[xo + v];
+                    if (PLAIN_OFF(p.refvec, nullptr)) refc = p.refvec[xo + v];
                 }
                 const double a = xv + delta, b = a + neg2delta;
                 const int col0 = ci.cost_joff - c;
@@ -510,9 +516,9 @@ __device__ __forceinline__ void sweep_body(const SweepParams& p, const int mode,
 #pragma unroll
             for (int r = 0; r < DM; ++r)
                 if (r < dim) jst[col0 + r] = (r == c) ? dv : 0.0;  // untouched rows: scalar * (e - e) = 0
-            if (!fin && ci.cost2_joff >= 0) jst[ci.cost2_joff] = dv;   // duplicated MinimumTime dt edge (nlp_functions.cpp:91-107)
+            if (!PLAIN && !fin && ci.cost2_joff >= 0) jst[ci.cost2_joff] = dv;   // duplicated MinimumTime dt edge (nlp_functions.cpp:91-107)
         }
-        if (fin && !ci.fixed && ci.cost2_joff >= 0) {   // Terminal[Partial]EqualityConstraint x_f - xref: one row per (active) component, scaled by w_eq (:1552)
+        if (!PLAIN && fin && !ci.fixed && ci.cost2_joff >= 0) {   // Terminal[Partial]EqualityConstraint x_f - xref: one row per (active) component, scaled by w_eq (:1552)
             const double a = xv + delta, b = a + neg2delta;
             const double dv = (scalar * ((a - ref) - (b - ref))) * p.w_eq;
             // the component's row inside the edge (TerminalPartialEqualityConstraint: active components only; an inactive one has no row and
@@ -544,9 +550,9 @@ __device__ __forceinline__ void sweep_body(const SweepParams& p, const int mode,
             }
             put_value(ci.cost_row, val);
             sq_acc += val * val;
-            if (!fin && ci.cost2_row >= 0) { put_value(ci.cost2_row, val); sq_acc += val * val; }
+            if (!PLAIN && !fin && ci.cost2_row >= 0) { put_value(ci.cost2_row, val); sq_acc += val * val; }
         }
-        if (fin && ci.cost2_row >= 0) {   // TerminalEqualityConstraint row (equality section: times w_eq)
+        if (!PLAIN && fin && ci.cost2_row >= 0) {   // TerminalEqualityConstraint row (equality section: times w_eq)
             const double val = (xv - ref) * p.w_eq;
             put_value(ci.cost2_row, val);
             sq_acc += val * val;
@@ -586,7 +592,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams& p, const int mode,
 #pragma unroll
         for (int e = 0; e < NX; ++e) rv[e] = xr[e];
         double rspec = 0.0;
-        if (p.refvec) {
+        if (PLAIN_OFF(p.refvec, nullptr)) {
 #pragma unroll
             for (int e = 0; e < NX; ++e) rv[e] = p.refvec[xo + ((reg || isfin) ? kb * S + e : 0)];
             rspec = p.refvec[xo + ((spec && js < NX) ? vspec : 0)];
@@ -639,16 +645,16 @@ __device__ __forceinline__ void sweep_body(const SweepParams& p, const int mode,
                 wf   = (js == i) ? p.mp.sqf[i] : wf;
                 reff = (js == i) ? xr[i] : reff;
             }
-            if (p.refvec && fin) reff = rspec;
+            if (PLAIN_OFF(p.refvec, nullptr) && fin) reff = rspec;
             const CompInfo ci{cA[0].x, cA[0].y, cA[0].z, cA[0].w, cB[0].x, cB[0].y, cB[0].z, cB[0].w};
             const double xv = xs[vspec];
             if (!fin && ci.cost_row >= 0) {   // (the x_f components' cost and bound rows: the regular slots of lane N - 1)
                 const double val = wf * (xv - reff);
                 put_value(ci.cost_row, val);
                 sq_acc += val * val;
-                if (ci.cost2_row >= 0) { put_value(ci.cost2_row, val); sq_acc += val * val; }
+                if (!PLAIN && ci.cost2_row >= 0) { put_value(ci.cost2_row, val); sq_acc += val * val; }
             }
-            if (fin && ci.cost2_row >= 0) {   // TerminalEqualityConstraint row (equality section: times w_eq)
+            if (!PLAIN && fin && ci.cost2_row >= 0) {   // TerminalEqualityConstraint row (equality section: times w_eq)
                 const double val = (xv - reff) * p.w_eq;
                 put_value(ci.cost2_row, val);
                 sq_acc += val * val;
@@ -787,7 +793,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams& p, const int mode,
             if constexpr (LEAN) kt.r[i] = val;
         }
         {
-            if (p.ineq_cols) {  // computeValuesActiveInequality (hyper_graph_optimization_problem_base.cpp:278-289)
+            if (PLAIN_OFF(p.ineq_cols, nullptr)) {  // computeValuesActiveInequality (hyper_graph_optimization_problem_base.cpp:278-289)
                 double xl_[NX];   // (a private copy: the function sees one address space at every call site)
 #pragma unroll
                 for (int i = 0; i < NX; ++i) xl_[i] = xs[base + i];
@@ -800,7 +806,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams& p, const int mode,
     }
     // (c) the final-stage inequality on x_f (TerminalBall): one lane
     {
-        if (p.fin_row >= 0 && tid == THREADS - 1) {
+        if (PLAIN_OFF(p.fin_row, -1) >= 0 && tid == THREADS - 1) {
             double cf = terminal_ball<NX>(xs + (p.N - 1) * S, xr, p.mp.fin);
             cf        = (cf < 0) ? 0.0 : cf * p.w_ineq;   // computeValuesActiveInequality
             put_value(p.fin_row, cf);
@@ -930,7 +936,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams& p, const int mode,
     if constexpr (LEAN) {
         if (keep && do_jac) *keep = kt;   // the residual just evaluated pairs with the Jacobian about to be written (like LmState::vbuf ^= 1)
     }
-    if (!do_jac || (p.skip_jac && mode >= 2)) return;
+    if (!do_jac || (PLAIN_OFF(p.skip_jac, 0) && mode >= 2)) return;
     if constexpr (NOJAC) return;   // residual-only instantiation (big-block family inside the LM loop: the Jacobian is big_stage_kernel's): no Jacobian code, a quarter of the registers
 
     // ---- combined sparse Jacobian (computeCombinedSparseJacobian, hyper_graph_optimization_problem_edge_based.cpp:1480-1753),
@@ -1177,7 +1183,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams& p, const int mode,
     }
     // (3) stage inequality rows (active rows only, explicit zero otherwise, :1568-1610)
     {
-        if (p.ineq_cols) {
+        if (PLAIN_OFF(p.ineq_cols, nullptr)) {
             for (int k = tid; k < p.N - 1; k += THREADS) {
                 double loc[NX];
 #pragma unroll
@@ -1200,7 +1206,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams& p, const int mode,
         }
     }
     if constexpr (NX <= 4) {   // final-stage inequality row on x_f (same rule: active row or explicit zeros)
-        if (p.fin_row >= 0 && tid == THREADS - 1) {
+        if (PLAIN_OFF(p.fin_row, -1) >= 0 && tid == THREADS - 1) {
             double loc[NX];
 #pragma unroll
             for (int i = 0; i < NX; ++i) loc[i] = xs[(p.N - 1) * S + i];
@@ -4756,9 +4762,14 @@ __device__ __forceinline__ int32_t* cu_row_of(int32_t* table)
 // same 1024 resident instances without the register spills of the 128-VGPR build -- VERDICT r3 item 1a) or 128 (two waves, 256 VGPRs).
 // DENSE (round 6): the instantiation for non-diagonal weights (four-wave shape only; a separate instantiation, so the diagonal problems' kernels carry none of its
 // registers) -- such handles ran every LM pass as two launches before.
-template <int DYN, int DEFECT, bool ARROW, bool LOOP, int NPC, int THREADS = SWEEP_THREADS, bool DENSE = false>
+// PLAIN: the headline problem class on the two-wave fixed-horizon shape (launch_pass_t decides from the handle's state at launch): no stage / final
+// inequality, no terminal equality or second cost row, no per-vertex references, no delta_out, not queue mode, no diagnostics (timeline, pass_timeline,
+// phase_cycles, stagger).  Their fields are never loaded and their tests, selects and registers are compiled out (PLAIN_OFF); the arithmetic is the general
+// instantiation's, operation for operation.
+template <int DYN, int DEFECT, bool ARROW, bool LOOP, int NPC, int THREADS = SWEEP_THREADS, bool DENSE = false, bool PLAIN = false>
 __global__ __launch_bounds__(THREADS, (THREADS == SWEEP_THREADS ? CORBO_HIP_PASS_WAVES : THREADS / 64)) void lm_pass_kernel(const FactorParams fp, const SweepParams sp)
 {
+    static_assert(!PLAIN || (LOOP && !ARROW && !DENSE && NPC > 0 && THREADS == 128), "the plain problem class exists for the two-wave, fixed-horizon, fixed-dt, diagonal-weights run-to-completion shape only");
     static_assert(!DENSE || THREADS == SWEEP_THREADS || THREADS == 128, "non-diagonal weights: the four-wave shape, or two waves WITHOUT the stage-centric component pass (its lean staging and re-evaluated rows are the diagonal problem's)");
     constexpr int BK_LANE = (THREADS > 128) ? 128 : THREADS - 1;   // the lane that keeps the CU's progress row (a spare lane of wave 2 / the last lane)
     using Dy = Dynamics<DYN>;
@@ -4804,7 +4815,7 @@ __global__ __launch_bounds__(THREADS, (THREADS == SWEEP_THREADS ? CORBO_HIP_PASS
         typedef const __attribute__((address_space(4))) Args* ArgsPtr;
         ArgsPtr ka = (ArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
         int tid_v = tid;
-        if (fp.stagger == -1 || (fp.cu_table && fp.batch <= 1024)) {   // before the first table-based priority: by dispatch generation, youngest first (age favours the oldest)
+        if (PLAIN_OFF(fp.stagger, 0) == -1 || (fp.cu_table && fp.batch <= 1024)) {   // before the first table-based priority: by dispatch generation, youngest first (age favours the oldest)
             switch (blockIdx.x >> 8) {
                 case 3: __builtin_amdgcn_s_setprio(3); break;
                 case 2: __builtin_amdgcn_s_setprio(2); break;
@@ -4812,14 +4823,14 @@ __global__ __launch_bounds__(THREADS, (THREADS == SWEEP_THREADS ? CORBO_HIP_PASS
                 default: __builtin_amdgcn_s_setprio(0); break;
             }
         }
-        if (fp.stagger > 0) {   // diagnostics: phase-shift the workgroups that share a CU
+        if (PLAIN_OFF(fp.stagger, 0) > 0) {   // diagnostics: phase-shift the workgroups that share a CU
             const long long t0 = clock64(), d = (long long)(blockIdx.x >> 8) * fp.stagger;
             while (clock64() - t0 < d) __builtin_amdgcn_s_sleep(16);
         }
 #pragma nounroll
         for (;;) {
             // (queue mode is a launch parameter, not an instantiation: one uniform branch per instance; the library carries half as many kernels)
-            const bool queue_mode = ((const FactorParams&)ka->f).queue != nullptr;
+            const bool queue_mode = !PLAIN && ((const FactorParams&)ka->f).queue != nullptr;
             if (queue_mode) {
                 asm volatile("" : "+v"(tid_v), "+s"(ka) : : "memory");   // (as in the pass loop: nothing is carried around this loop either)
                 const FactorParams& fq = (const FactorParams&)ka->f;
@@ -4846,9 +4857,9 @@ __global__ __launch_bounds__(THREADS, (THREADS == SWEEP_THREADS ? CORBO_HIP_PASS
                 asm volatile("" : "+s"(inst_v), "+v"(tid_v), "+s"(ka) : : "memory");  // nothing derived from them is carried around the loop
                 const FactorParams& fpl = (const FactorParams&)ka->f;
                 const SweepParams& spl  = (const SweepParams&)ka->s;
-                const bool stamp = fpl.pass_timeline && inst_v == fpl.pass_timeline_inst && tid_v == 0 && pass < 64;
+                const bool stamp = PLAIN_OFF(fpl.pass_timeline, nullptr) && inst_v == fpl.pass_timeline_inst && tid_v == 0 && pass < 64;
                 if (stamp) fpl.pass_timeline[2 * pass] = clock64();
-                const bool pcyc = fpl.phase_cycles && tid_v == 0;   // (diagnostics: per-instance phase totals, corbo_hip_get_phase_cycles)
+                const bool pcyc = PLAIN_OFF(fpl.phase_cycles, nullptr) && tid_v == 0;   // (diagnostics: per-instance phase totals, corbo_hip_get_phase_cycles)
                 long long pc_t0 = 0;
                 if (pcyc) pc_t0 = clock64();
                 if (pass > 0) {
@@ -4867,7 +4878,7 @@ __global__ __launch_bounds__(THREADS, (THREADS == SWEEP_THREADS ? CORBO_HIP_PASS
                 }
                 constexpr bool TWOW = (THREADS <= 128) && !DENSE;   // two-wave shape: Jacobian stream-out and bookkeeping ride inside the factor phase (factor_body, after_gather); non-diagonal weights: the sweep phase stores and streams everything itself
                 int scv[2 * Dy::NX + Dy::NU + 1];   // (two-wave shape) Jacobian offsets of lane k's defect edge: requested by the sweep phase, used by this pass's factor phase as well
-                sweep_body<DYN, DEFECT, true, DENSE, false, THREADS>(spl, mode, spl.active_count, sl, xs, red, cs, jst, inst_v, tid_v, pass > 0, &keep, TWOW && max_passes > 0, TWOW ? scv : nullptr);   // (active_count: per-pass launches only)
+                sweep_body<DYN, DEFECT, true, DENSE, false, THREADS, false, false, PLAIN>(spl, mode, spl.active_count, sl, xs, red, cs, jst, inst_v, tid_v, pass > 0, &keep, TWOW && max_passes > 0, TWOW ? scv : nullptr);   // (active_count: per-pass launches only)
                 __threadfence_block();
                 __syncthreads();
                 if (stamp) fpl.pass_timeline[2 * pass + 1] = clock64();
@@ -4923,6 +4934,8 @@ __global__ __launch_bounds__(THREADS, (THREADS == SWEEP_THREADS ? CORBO_HIP_PASS
                         bk_publish();
                     }
                 };
+                // (PLAIN stops at the sweep phase and this loop: the factor phase is compiled under fp contract(fast), where the backend fuses a multiply with an add of
+                //  the same basic block -- taking a branch out of it changes which pairs are fused, i.e. the rounding.  Measured: its PLAIN form gave other bits.)
                 // (loop_passes = 0: ONE pass per launch -- the per-pass mode of corbo_hip_solve and the profiling mode; the trial iterate then
                 //  goes to HBM for the next launch instead of staying in the LDS array the next sweep phase evaluates it from)
                 factor_body<Dy::NX, Dy::NU, THREADS, ARROW, NPC, DENSE, false, TWOW>(fpl, sl, smem, inst_v, tid_v, j_fresh, max_passes > 0 ? xs : nullptr, &spl, &keep, max_passes > 0 || j_fresh, hook, TWOW ? scv : nullptr, &smask);
@@ -4954,7 +4967,7 @@ __global__ __launch_bounds__(THREADS, (THREADS == SWEEP_THREADS ? CORBO_HIP_PASS
             }
             if (tid_v == 0 && !sl->done && fe.unfinished_flag) *(volatile int32_t*)fe.unfinished_flag = 1;  // pass limit hit
             asm volatile("" : "+s"(ka) : : "memory");
-            if (((const FactorParams&)ka->f).queue == nullptr) break;
+            if (PLAIN || ((const FactorParams&)ka->f).queue == nullptr) break;
         }
     }
 }
@@ -5732,6 +5745,7 @@ bool launch_pass_t(const FactorParams& fp, const SweepParams& sp, hipStream_t st
         if (two) {
             const dim3 b(128);
             if (fp.dt_free) hipLaunchKernelGGL((lm_pass_kernel<DYN, DEFECT, true, true, 0, 128>), dim3(grid), b, lds, stream, fp, sp);
+            else if (pass_kernel_is_plain(fp, sp)) hipLaunchKernelGGL((lm_pass_kernel<DYN, DEFECT, false, true, 101, 128, false, true>), dim3(grid), b, lds, stream, fp, sp);   // ... and the plain problem class: no option code
             else if (fp.N == 100) hipLaunchKernelGGL((lm_pass_kernel<DYN, DEFECT, false, true, 101, 128>), dim3(grid), b, lds, stream, fp, sp);   // the headline horizon: LDS strides as immediates, zero neighbour slot
             else hipLaunchKernelGGL((lm_pass_kernel<DYN, DEFECT, false, true, 0, 128>), dim3(grid), b, lds, stream, fp, sp);
         }

@@ -147,6 +147,8 @@ struct FactorParams {
     int32_t bt_snap_stride;
     int32_t bt_waves;             // handle option "bt_waves": 0 = launch_bt_t chooses by batch size, 2 / 3 = the instantiation for that many workgroups per CU (A/B)
     int32_t num_cus;              // compute units of the device (launch_bt_t: how many instances are resident at once)
+    int32_t plain_ok;             // run-to-completion kernel: handle option "plain_kernel" is on AND no component of the structure carries a second cost row (terminal
+                                  //   equality, duplicated dt edge) -- what pass_kernel_is_plain cannot see in the parameter blocks themselves
 };
 
 // Reject-streak speculation of the big-block family (big_spec_kernel; VERDICT r3 item 2 a).  An instance whose trial step was rejected re-factorises the
@@ -298,6 +300,18 @@ void launch_upload_instance(const UploadParams& p, hipStream_t stream);
 bool launch_stage_jacobian_dump(const corbo_hip_problem_desc& d, const FactorParams& fp, const SweepParams& sp, double* jac_out, hipStream_t stream);
 bool device_kernels_exist(const corbo_hip_problem_desc& d);   // host-only: the dispatch has kernels for d (corbo_hip_create's gate)
 bool launch_pass(const corbo_hip_problem_desc& d, const FactorParams& fp, const SweepParams& sp, hipStream_t stream);
+// Does this launch of the fused pass run the PLAIN instantiation (kernels.hip, lm_pass_kernel<.., PLAIN>)?  Decided from the parameter blocks of the launch alone, by
+// launch_pass_t and -- for corbo_hip_stats::plain_kernel -- by the caller: the branch the general code would take is the two-wave, fixed-dt, diagonal-weights one at
+// N = 100 (the only shape with the instantiation), run to completion, and none of the options the instantiation compiles out is on.
+inline bool pass_kernel_is_plain(const FactorParams& fp, const SweepParams& sp)
+{
+    if (!fp.plain_ok || fp.loop_passes <= 0) return false;
+    if (fp.N != 100 || fp.nx > 4 || fp.N + fp.nx + 1 > 128 || fp.pass_threads == 256 || fp.dt_free || fp.wdense_mask || sp.n_xedges > 0) return false;
+    if (fp.ineq_cols || sp.ineq_cols || fp.fin_row >= 0 || sp.fin_row >= 0 || sp.fin_eq_dim > 0) return false;   // stage / final inequality, terminal equality
+    if (sp.refvec || fp.delta_out || sp.xtasks || sp.skip_jac || fp.queue) return false;
+    if (fp.timeline || sp.timeline || fp.pass_timeline || fp.phase_cycles || fp.stagger != 0) return false;     // diagnostics
+    return true;
+}
 bool launch_band_factor(const FactorParams& fp, const BandParams& bp, hipStream_t stream);
 // Block-tridiagonal route (lm_bt_kernel): what corbo_hip_create asks before it builds the tables -- block size s = nx + nu, free dt, grid points, the
 // padded Jacobian / residual lengths, the dynamics' cache doubles per grid state.  0 = no such kernel (horizon, LDS); else the rounds its assembly holds.

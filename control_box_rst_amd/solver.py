@@ -243,7 +243,8 @@ class BatchedLevenbergMarquardt:
         self._check(self.lib.corbo_hip_resample_into(self._h, dst._h, len(si), _ip(si), _ip(di)), "corbo_hip_resample_into")
 
     def set_option(self, name: str, value: int):
-        """Diagnostics / test hooks of the handle (corbo_hip_set_option): pass_limit, run_to_completion, pass_timeline, sweep_timeline."""
+        """Diagnostics / test hooks of the handle (corbo_hip_set_option): pass_limit, run_to_completion, pass_timeline, sweep_timeline, async_lanes,
+        plain_kernel (0: the general fused pass kernel also where the plain instantiation applies; get_stats()["plain_kernel"] says which one ran), ..."""
         self._check(self.lib.corbo_hip_set_option(self._h, name.encode(), int(value)), "corbo_hip_set_option")
 
     def set_profiling(self, enable: bool):

@@ -277,6 +277,8 @@ typedef struct corbo_hip_stats {
     float   sweep_ms;           /* accumulated time of the edge/Jacobian sweep kernel inside it (0 if not profiled) */
     float   factor_ms;          /* accumulated time of the assemble/factor/solve kernel (0 if not profiled) */
     int32_t inner_loop_cuts;    /* instances whose inner loop was cut after 64 consecutive rejections (status ERROR); 0 in every test */
+    int32_t plain_kernel;       /* 1: the last solve's run-to-completion launch was the plain instantiation of the fused pass kernel (option "plain_kernel");
+                                 * same results bit for bit, fewer issued instructions.  (Sits in what was padding: the struct's size and offsets are unchanged.) */
     int64_t counted_iterations; /* of lm_iterations (and of factorizations, one each): outer iterations that followed a converged step
                                  * (|delta| <= eps2 / 2) and were COUNTED, not executed (option "ff_converged", default on; the reference
                                  * executes them and changes nothing a caller sees, levenberg_marquardt_sparse.cpp:129-154).  Rates of
@@ -648,6 +650,10 @@ int corbo_hip_eval_stage_function(int id, int dim, int n, const double* v, const
  *   "ff_converged"      0: compute the outer iterations that follow a converged step instead of counting them (A/B and tests)
  *   "lag_priority"      0: no lag-based issue priority in the run-to-completion kernel
  *   "phase_cycles"      1: per-instance phase totals of the run-to-completion kernel (corbo_hip_get_phase_cycles)
+ *   "plain_kernel"      1 (default): a run-to-completion solve of the plain problem class at the headline horizon -- N = 100, two-wave shape, fixed dt, diagonal
+ *                       weights; no stage / final inequality, terminal equality, per-vertex references, instance queue or diagnostic option -- launches the
+ *                       instantiation of the fused pass kernel that has those options compiled out (same results bit for bit); 0: always the
+ *                       general kernel (A/B, tests).  corbo_hip_stats::plain_kernel says which one the last solve ran.
  *   "raw_stamps"        1: "pass_timeline" prints raw stamp offsets (development builds that re-purpose the stamp slots)
  *   "band_wide"         1: the band route (integral-form constraint edges / control-deviation term) keeps the eight-wave factor kernel for every
  *                       half-bandwidth; 0 (default): half-bandwidths up to 7 take the one-wave-per-instance kernel
