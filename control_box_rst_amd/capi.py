@@ -116,6 +116,7 @@ EXPORTED_SYMBOLS = (
     "corbo_hip_device_count", "corbo_hip_shard_bounds", "corbo_hip_device_row_stride",
     "corbo_hip_set_references", "corbo_hip_set_reference_trajectory", "corbo_hip_hessian_nnz", "corbo_hip_hessian_structure", "corbo_hip_eval_hessians", "corbo_hip_eval_hessians_views", "corbo_hip_linear_form_structure", "corbo_hip_eval_linear_form", "corbo_hip_eval_objective_gradient",
     "corbo_hip_sizeof", "corbo_hip_set_previous_control", "corbo_hip_get_phase_cycles", "corbo_hip_create_routed", "corbo_hip_create_weighted", "corbo_hip_factor_route", "corbo_hip_stage_function_kind", "corbo_hip_eval_stage_function",
+    "corbo_hip_long_factor_plan",
 )
 
 
@@ -209,6 +210,8 @@ def load() -> C.CDLL:
     lib.corbo_hip_linear_form_structure.argtypes = [C.POINTER(ProblemDesc), ip, ip, ip, ip]
     lib.corbo_hip_eval_linear_form.argtypes = [H, dp, dp, dp]
     lib.corbo_hip_eval_objective_gradient.argtypes = [H, dp, dp]
+    if hasattr(lib, "corbo_hip_long_factor_plan"):   # (an older build loaded through CORBO_HIP_LIB has none)
+        lib.corbo_hip_long_factor_plan.argtypes = [C.POINTER(ProblemDesc), C.POINTER(C.c_int32 * 4)]
     lib.corbo_hip_last_error.argtypes = []
     lib.corbo_hip_last_error.restype = C.c_char_p
     _lib = lib

@@ -365,6 +365,20 @@ try {
 }
 ABI_CATCH
 
+int corbo_hip_long_factor_plan(const corbo_hip_problem_desc* desc, int32_t out[4])
+try {
+    if (!desc || !out) return fail(CORBO_HIP_ERR_INVALID, "null argument");
+    Structure S;
+    std::string err = build_structure(*desc, S);
+    if (!err.empty()) return fail(CORBO_HIP_ERR_INVALID, err);
+    LongFactorPlan pl;
+    if (S.has_extra() || !long_factor_plan_for(*desc, &pl))
+        return fail(CORBO_HIP_ERR_INVALID, "no long-horizon stage factorisation for this descriptor (256 < N <= 1024, nx <= 4, no extra edges)");
+    out[0] = pl.threads; out[1] = pl.wg_per_cu; out[2] = pl.lds_bytes; out[3] = pl.dense;
+    return CORBO_HIP_OK;
+}
+ABI_CATCH
+
 int corbo_hip_get_structure(const corbo_hip_problem_desc* desc, int32_t* rows, int32_t* cols)
 try {
     if (!desc || !rows || !cols) return fail(CORBO_HIP_ERR_INVALID, "null argument");

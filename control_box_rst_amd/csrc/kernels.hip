@@ -2717,12 +2717,7 @@ __global__ __launch_bounds__(THREADS, MINW) void factor_long_kernel(const Factor
     __syncthreads();
     lm_state_out(p.st + inst, &sl_, threadIdx.x);
 }
-// LDS of the HYB variant: D (packed), W_a, W_b, rhs per block, the reduction scratch of sixteen waves, the border column (free dt)
-template <int NX, int NU>
-__host__ __device__ constexpr size_t factor_long_hyb_lds_doubles(int N, bool arrow)
-{
-    return (size_t)(NX * (NX + 1) / 2 + 2 * NX * NX + NX) * (N | 1) + 8 * 16 + (arrow ? (size_t)NX * (N | 1) : 0) + 2;
-}
+// (LDS of the HYB variant: factor_long_hyb_lds_doubles, kernels.hpp)
 template <int NX, int NU>
 __host__ __device__ constexpr size_t factor_long_work_doubles(int N, bool arrow)
 {
@@ -5781,19 +5776,18 @@ bool launch_factor_a(const FactorParams& p, hipStream_t stream)
     lds = ((lds + 15) & ~(size_t)15) + sizeof(LmState);                                      // + LM state
     if (p.N > LONG_HORIZON) {   // long horizon: workspace in HBM
         if (p.N > LONG_HORIZON_MAX || !p.work) return false;
-        const size_t hyb = sizeof(double) * factor_long_hyb_lds_doubles<NX, NU>(p.N, ARROW);
-        if (hyb + sizeof(LmState) + 64 <= (size_t)160 * 1024) {   // the state-block arrays fit the LDS of a CU: only the controls' arrays stay in the HBM workspace
-            auto go = [&](auto kernel, int threads) {
-                set_max_dynamic_lds(kernel, 160 * 1024 - (int)sizeof(LmState) - 64);
-                hipLaunchKernelGGL(kernel, dim3(p.batch), dim3(threads), hyb, stream, p);
+        const LongFactorPlan plan = long_factor_plan(NX, p.N, ARROW, p.wdense_mask != 0, p.pass_threads);   // kernels.hpp: the one place that decides
+        if (plan.wg_per_cu > 0) {   // the state-block arrays fit the LDS of a CU: only the controls' arrays stay in the HBM workspace
+            auto go = [&](auto kernel) {
+                set_max_dynamic_lds(kernel, LONG_FACTOR_LDS_MAX);
+                hipLaunchKernelGGL(kernel, dim3(p.batch), dim3(plan.threads), (size_t)plan.lds_bytes, stream, p);
             };
-            const bool two_per_cu = 2 * (hyb + sizeof(LmState) + 64) <= (size_t)160 * 1024;
-            if (p.wdense_mask) go(factor_long_kernel<NX, NU, ARROW, true, true>, 1024);
-            else if (p.N <= 512 && p.pass_threads != 1024) {   // (option pass_threads = 1024: the sixteen-wave shape, A/B)
-                if (two_per_cu) go(factor_long_kernel<NX, NU, ARROW, false, true, 512, 4>, 512);
-                else go(factor_long_kernel<NX, NU, ARROW, false, true, 512, 2>, 512);
+            if (plan.dense) go(factor_long_kernel<NX, NU, ARROW, true, true>);
+            else if (plan.threads == 512) {   // (option pass_threads = 1024: the sixteen-wave shape, A/B)
+                if (plan.minw == 4) go(factor_long_kernel<NX, NU, ARROW, false, true, 512, 4>);
+                else go(factor_long_kernel<NX, NU, ARROW, false, true, 512, 2>);
             }
-            else go(factor_long_kernel<NX, NU, ARROW, false, true>, 1024);
+            else go(factor_long_kernel<NX, NU, ARROW, false, true>);
             return true;
         }
         if (p.wdense_mask) hipLaunchKernelGGL((factor_long_kernel<NX, NU, ARROW, true>), dim3(p.batch), dim3(1024), 0, stream, p);   // non-diagonal weights
@@ -6247,6 +6241,15 @@ size_t factor_work_doubles(const corbo_hip_problem_desc& d)
         });
     }
     return 0;
+}
+
+bool long_factor_plan_for(const corbo_hip_problem_desc& d, LongFactorPlan* out)
+{
+    if (big_family_dims(d.nx, d.nu) || d.N <= LONG_HORIZON || d.N > LONG_HORIZON_MAX) return false;
+    if (!with_small_shape(d.nx, d.nu, false, [](auto, auto) { return true; })) return false;
+    const bool arrow = (d.grid == CORBO_HIP_GRID_FD_VARIABLE || d.grid == CORBO_HIP_GRID_MS_VARIABLE);
+    *out = long_factor_plan(d.nx, d.N, arrow, d.weights_dense != 0, 0);
+    return true;
 }
 
 size_t factor_lds_bytes(const corbo_hip_problem_desc& d, const FactorParams& p)

@@ -323,6 +323,39 @@ size_t sweep_lds_bytes(const SweepParams& p, int nc);
 // Small-block families with horizons up to 256 grid points assemble the Jacobian values in an LDS staging area (STAGE in sweep_body); the
 // device-internal value layout carries one pad double per defect block for exactly those (corbo_hip_create).
 constexpr bool jacobian_staged_in_lds(int nx, int N) { return nx <= 4 && N <= 256; }
+// Long horizons (256 < N <= 1024) of the small-block families: which shape of factor_long_kernel a pass launches.  One host function, used by the launcher
+// (launch_factor_a) and by corbo_hip_long_factor_plan, so that a test can ask on which side of a switch a horizon lies without a GPU.
+//   HYB: the state-block arrays -- D (packed), W_a, W_b, rhs per block, the reduction scratch of sixteen waves, the border column (free dt) -- in LDS, only the
+//   eliminated controls' arrays in the HBM workspace; taken wherever one workgroup's arrays + LM state fit the 160 KB of a CU
+constexpr int LONG_FACTOR_LDS_CU  = 160 * 1024;
+constexpr int LONG_FACTOR_LDS_MAX = LONG_FACTOR_LDS_CU - (int)sizeof(LmState) - 64;   // dynamic LDS a HYB launch may ask for
+constexpr size_t factor_long_hyb_lds_doubles(int nx, int N, bool arrow)
+{
+    return (size_t)(nx * (nx + 1) / 2 + 2 * nx * nx + nx) * (N | 1) + 8 * 16 + (arrow ? (size_t)nx * (N | 1) : 0) + 2;
+}
+struct LongFactorPlan {
+    int32_t threads;     // workgroup size: 512 (eight waves, N <= 512) or 1024
+    int32_t minw;        // second __launch_bounds__ argument of the instantiation: 4 (128 VGPRs) or 2
+    int32_t wg_per_cu;   // workgroups whose state-block arrays the LDS of a CU admits: 2, 1, or 0 = none (HBM workspace, no dynamic LDS)
+    int32_t lds_bytes;   // dynamic LDS of the launch
+    int32_t dense;       // the DENSE instantiation (non-diagonal weights)
+};
+inline LongFactorPlan long_factor_plan(int nx, int N, bool arrow, bool dense, int pass_threads)
+{
+    const size_t hyb = sizeof(double) * factor_long_hyb_lds_doubles(nx, N, arrow);
+    const size_t one = hyb + sizeof(LmState) + 64;
+    LongFactorPlan pl{1024, 4, 0, 0, dense ? 1 : 0};
+    if (one > (size_t)LONG_FACTOR_LDS_CU) return pl;
+    pl.wg_per_cu = (2 * one <= (size_t)LONG_FACTOR_LDS_CU) ? 2 : 1;
+    pl.lds_bytes = (int32_t)hyb;
+    if (!dense && N <= 512 && pass_threads != 1024) {
+        pl.threads = 512;
+        pl.minw = (pl.wg_per_cu == 2) ? 4 : 2;
+    }
+    return pl;
+}
+// host-only: the plan of descriptor d with the default options; false = d does not run factor_long_kernel (horizon, big-block family, no such block shape)
+bool long_factor_plan_for(const corbo_hip_problem_desc& d, LongFactorPlan* out);
 size_t factor_lds_bytes(const corbo_hip_problem_desc& d, const FactorParams& p);
 // doubles of HBM workspace per instance the factor kernel needs (0 for the LDS-resident small-block kernel)
 size_t factor_work_doubles(const corbo_hip_problem_desc& d);

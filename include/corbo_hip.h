@@ -304,6 +304,13 @@ int corbo_hip_get_dims(const corbo_hip_problem_desc* desc, corbo_hip_dims* dims)
  * Needs no GPU. */
 int corbo_hip_get_structure(const corbo_hip_problem_desc* desc, int32_t* rows, int32_t* cols);
 
+/* Which long-horizon factor kernel a solve of `desc` launches (small-block families, 256 < N <= 1024; default options).  out[0]: threads per
+ * workgroup (512 / 1024); out[1]: workgroups per CU whose state-block arrays the LDS admits (2 / 1; 0 = the whole workspace in HBM);
+ * out[2]: dynamic LDS bytes of the launch; out[3]: 1 = the instantiation for non-diagonal weights.  The launcher takes its decision from the
+ * same function.  CORBO_HIP_ERR_INVALID for every descriptor that does not run that kernel (N <= 256, N > 1024, nx > 4, extra edges).
+ * Needs no GPU. */
+int corbo_hip_long_factor_plan(const corbo_hip_problem_desc* desc, int32_t out[4]);
+
 /* Initial trajectory exactly as the grid writes it into the vertices before the first solve
  * (FullDiscretizationGridBase::initializeSequences, full_discretization_grid_base.cpp:134-179): linear
  * interpolation x0 -> xf, u = 0, dt = dt_ref.  x0, xf: [batch][nx]; x_out: [batch][nv].  Host-only helper. */

@@ -119,6 +119,7 @@ class Case(NamedTuple):
 RATE = {"unicycle": (0.3, 0.3), "vdp": (0.7,), "cartpole": (0.5,), "quad": (4.0, 2.0, 2.0, 2.0), "int3t": (3.0,)}
 EQ_LIN = {"vdp": (0.3, -0.2, 0.05, 0.1), "int3t": (0.01, 0.02, 0.0, 0.05, 0.0), "unicycle": (0.3, -0.2, 0.1, 0.05, 0.02, 0.1)}
 _BASE_WEIGHTS = {"unicycle": problems.UNICYCLE_WEIGHTS, "vdp": problems.VDP_WEIGHTS, "cartpole": problems.BENCHMARK_WEIGHTS, "par3": problems.BENCHMARK_WEIGHTS,
+                 "par2": problems.BENCHMARK_WEIGHTS, "int3": problems.INT3_WEIGHTS, "cartpolet": problems.DINT_WEIGHTS,
                  "int3t": problems.INT3_WEIGHTS, "dint": problems.DINT_WEIGHTS, "quad": problems.QUAD_WEIGHTS, "quadt": problems.QUAD_WEIGHTS, "pquad": problems.QUAD_WEIGHTS}
 
 
@@ -133,7 +134,7 @@ def _dense_weights(d, seed):
 
 
 def make_desc(family: str, N: int):
-    """family = base[+extra]*: base one of unicycle, vdp, cartpole, par3, unicyclems, int3t, dint, quad, quadt, pquad; extras rate, eqlin (trapezoidal
+    """family = base[+extra]*: base one of unicycle, vdp, cartpole, cartpolet, par2, par3, unicyclems, int3, int3t, dint, quad, quadt, pquad; extras rate, eqlin (trapezoidal
     integral equality), dense (non-diagonal weights)."""
     base, *extras = family.split("+")
     if base == "unicycle":
@@ -145,8 +146,19 @@ def make_desc(family: str, N: int):
         d = problems.vdp_desc(N=N)
     elif base == "cartpole":
         d = problems.benchmark_desc("cartpole", N=N)
+    elif base == "cartpolet":    # the cart-pole, time-optimal like int3t: FiniteDifferencesVariableGrid, MinimumTime, x_f fixed -- shape (4, 1) with a free dt
+        d = problems.benchmark_desc("cartpole", N=N)
+        d.grid, d.stage_cost, d.final_cost, d.xf_fixed_mask = capi.GRID_FD_VARIABLE, capi.COST_MIN_TIME_LSQ, 0, 0b1111
+        d.dt_lb, d.dt_ub = 0.01, 10.0
+        for i in range(d.nx):
+            d.q_diag[i] = d.qf_diag[i] = 0.0
+        d.r_diag[0] = 0.0
+    elif base == "par2":
+        d = problems.parallel_integrator_desc(2, N=N)
     elif base == "par3":
         d = problems.parallel_integrator_desc(3, N=N)
+    elif base == "int3":         # the fixed-dt serial integrator: shape (3, 1)
+        d = problems.int3_desc(N=N, dt=0.1)
     elif base == "int3t":        # time-optimal: the free dt is the arrowhead of H
         d = problems.int3_desc(N=N, dt=0.1, time_optimal=True)
     elif base == "dint":
@@ -190,7 +202,7 @@ BATCH = 3
 # every parameter but a free dt: close enough to a solution that the first pass is accepted at every
 # horizon of the table, rough enough that the step is no smaller than a twentieth of the iterate (eta is computed from fl(x_0 + delta) - x_0) and that every
 # block of H carries generic values.  test_oracle_linear_solve.py asserts both on every input.
-START = {"unicycle": (1.0, 0.1), "vdp": (1.0, 0.1), "cartpole": (1.0, 0.1), "par3": (1.0, 0.1), "unicyclems": (0.0, 0.3), "int3t": (0.3, 0.03), "dint": (0.3, 0.03),
+START = {"unicycle": (1.0, 0.1), "vdp": (1.0, 0.1), "cartpole": (1.0, 0.1), "par3": (1.0, 0.1), "par2": (1.0, 0.1), "int3": (1.0, 0.1), "cartpolet": (0.3, 0.03), "unicyclems": (0.0, 0.3), "int3t": (0.3, 0.03), "dint": (0.3, 0.03),
          "unicycle+rate": (1.0, 0.3), "cartpole+rate": (1.0, 0.3), "unicycle+rate+eqlin+dense": (1.0, 0.3), "quad": (1.0, 0.3), "quad+rate": (0.3, 0.1), "pquad": (1.0, 0.1), "quadt": (1.0, 0.1)}
 
 
@@ -212,7 +224,7 @@ def make_start(case: Case, O):
         x0, xf = np.zeros((B, 6)), np.zeros((B, 6))
         x0[:, :2] = rng.uniform(-0.2, 0.2, (B, 2))
         xf[:, :2] = np.array([2.0, 1.0]) + rng.uniform(-0.3, 0.3, (B, 2))
-    elif base in ("int3t", "dint"):
+    elif base in ("int3t", "dint", "cartpolet"):
         x0 = np.zeros((B, nx))
         x0[:, 0] = rng.uniform(-0.3, 0.3, B)
         xf = np.zeros((B, nx))
@@ -286,6 +298,23 @@ BT_HORIZONS = (3, 4, 5, 8, 9, 16, 17, 33, 64, 65, 128, 129, 200, 256)
 # factor_long_kernel keeps the state-block arrays in LDS where 27 (N | 1) + 130 doubles fit 160 KB (unicycle: N <= 751, launch_factor_a) and works in the
 # HBM workspace beyond: 700 / 800 are one horizon on each side; 257 .. 512 run eight waves (two resp. one workgroup per CU), 513 sixteen.
 LONG_HORIZONS = (257, 512, 513, 700, 800, 1024)
+# ... and the same for every block shape (nx, nu, free dt) the build compiles factor_long_kernel for: the smallest horizons on each side of every switch of
+# launch_factor_a that the shape can reach -- two workgroups' state blocks per CU | one (nx = 3: 373 | 374, with a free dt 335 | 336; nx = 2: 775 | 776, with a
+# free dt 671 | 672 -- there the sixteen-wave instantiation is the same on both sides, what changes is how many workgroups a CU holds), eight | sixteen waves
+# (512 | 513), LDS | HBM workspace (nx = 3: 751 | 752, free dt 677 | 678; nx = 4: 441 | 442, free dt 405 | 406).  corbo_hip_long_factor_plan reports the
+# launcher's decision; test_oracle_linear_solve.py::test_table_covers_the_listed_paths asserts against it that every switch is straddled (docs/measurements/r10.md).
+LONG_SHAPE_HORIZONS = {
+    "vdp": (257, 512, 513, 775, 776, 1024),                          # (2, 1)
+    "par2": (257, 512, 513, 775, 776, 1024),                         # (2, 2)
+    "dint": (671, 672),                                              # (2, 1), free dt (the other horizons: LONG_HORIZONS)
+    "int3": (257, 373, 374, 512, 513, 751, 752, 1024),               # (3, 1)
+    "par3": (257, 373, 374, 512, 513, 751, 752, 1024),               # (3, 3)
+    "unicyclems": (257, 373, 374, 513, 751, 752),                    # (3, 2), shooting grid, RK4 (512: the unicycle of LONG_HORIZONS)
+    "int3t": (257, 335, 336, 512, 513, 677, 678, 1024),              # (3, 1), free dt
+    "cartpole": (257, 441, 442, 512, 513, 1024),                     # (4, 1)
+    "cartpolet": (257, 405, 406, 1024),                              # (4, 1), free dt
+}
+LONG_DENSE = (("cartpole+dense", 300), ("cartpole+dense", 500), ("par3+dense", 700), ("par3+dense", 800), ("vdp+dense", 1024))
 
 
 def _cases():
@@ -301,6 +330,11 @@ def _cases():
             c.append(Case("long", fam, N, expect=capi.FACTOR_STAGE_CR))
     c.append(Case("long", "unicycle+dense", 300, expect=capi.FACTOR_STAGE_CR))
     c.append(Case("long", "unicycle+dense", 800, expect=capi.FACTOR_STAGE_CR))
+    for fam, horizons in LONG_SHAPE_HORIZONS.items():
+        for N in horizons:
+            c.append(Case("long", fam, N, expect=capi.FACTOR_STAGE_CR))
+    for fam, N in LONG_DENSE:
+        c.append(Case("long", fam, N, expect=capi.FACTOR_STAGE_CR))
     for fam in ("unicycle+rate", "vdp+eqlin", "cartpole+rate", "int3t+eqlin"):
         for N in BT_HORIZONS:
             for waves in (2, 3):
@@ -334,6 +368,8 @@ def _rejecting():
         c.append(Case("cr", fam, N, start=start, expect=CR))
     for seed in (1, 2):
         c.append(Case("long", "unicycle", 257, start=("perturbed", 0.0, seed, 4.0), expect=CR))
+    c.append(Case("long", "cartpole", 442, start=("perturbed", 0.3, 1, 16.0), expect=CR))   # nx = 4, HBM workspace below 512 grid points
+    c.append(Case("long", "int3t", 336, start=("perturbed", 0.0, 0, 2.0), expect=CR))       # free dt, one workgroup per CU
     xe = (("unicycle+rate", 6, ("perturbed", 0.0, 0)), ("unicycle+rate", 12, ("perturbed", 0.0, 0)), ("unicycle+rate", 40, ("perturbed", 0.02, 0)),
           ("unicycle+rate", 200, ("perturbed", 0.02, 4)), ("cartpole+rate", 12, ("perturbed", 0.0, 1)), ("cartpole+rate", 40, ("perturbed", 0.0, 5)))
     for fam, N, start in xe:

@@ -88,6 +88,52 @@ def test_invalid_descriptors_are_rejected(lib):
     assert solver.get_dims(d).lsq == 0   # plain objective edges are no rows of the LM residual
 
 
+def _long_plan(lib, d):
+    out = (C.c_int32 * 4)()
+    rc = lib.corbo_hip_long_factor_plan(C.byref(d), C.byref(out))
+    return rc, tuple(out)
+
+
+def test_long_factor_plan_is_the_launchers_arithmetic(lib):
+    """corbo_hip_long_factor_plan (host only) against the layout written out here: c (N | 1) + 130 doubles with c = nx (nx + 1) / 2 + 2 nx^2 + nx, nx (N | 1) more
+    with a free dt; one workgroup fits when those bytes + the LM state (128) + 64 are within 160 KB, two when twice that is; eight waves up to 512 grid points;
+    non-diagonal weights and the HBM workspace always run sixteen waves."""
+    def expect(nx, N, free, dense):
+        c = nx * (nx + 1) // 2 + 2 * nx * nx + nx + (nx if free else 0)
+        lds = 8 * (c * (N | 1) + 130)
+        fit = (lds + 128 + 64 <= 160 * 1024) + (2 * (lds + 128 + 64) <= 160 * 1024)
+        return (512 if (N <= 512 and fit and not dense) else 1024, fit, lds if fit else 0, int(dense))
+
+    makers = {(2, 1, False): lambda N: problems.vdp_desc(N=N), (2, 1, True): lambda N: problems.dint_desc(N=N), (2, 2, False): lambda N: problems.parallel_integrator_desc(2, N=N),
+              (3, 1, False): lambda N: problems.int3_desc(N=N), (3, 1, True): lambda N: problems.int3_desc(N=N, time_optimal=True),
+              (3, 2, False): lambda N: problems.unicycle_desc(N=N), (3, 3, False): lambda N: problems.parallel_integrator_desc(3, N=N),
+              (4, 1, False): lambda N: problems.benchmark_desc("cartpole", N=N)}
+    for (nx, nu, free), mk in makers.items():
+        for N in (257, 335, 336, 373, 374, 405, 406, 441, 442, 512, 513, 671, 672, 677, 678, 751, 752, 775, 776, 1000, 1023, 1024):
+            d = mk(N)
+            assert (d.nx, d.nu) == (nx, nu)
+            assert _long_plan(lib, d) == (0, expect(nx, N, free, False)), (nx, nu, free, N)
+            if not free:
+                d.weights_dense = 1
+                for i in range(nx):
+                    d.q_sqrt[i * nx + i] = 1.0
+                assert _long_plan(lib, d) == (0, expect(nx, N, free, True)), (nx, nu, free, N, "dense")
+    # the switches themselves: the last horizon with two workgroups per CU | the last with the state blocks in LDS
+    assert [_long_plan(lib, problems.unicycle_desc(N=N))[1][:2] for N in (373, 374, 512, 513, 751, 752)] == [(512, 2), (512, 1), (512, 1), (1024, 1), (1024, 1), (1024, 0)]
+    assert [_long_plan(lib, problems.int3_desc(N=N, time_optimal=True))[1][:2] for N in (335, 336, 677, 678)] == [(512, 2), (512, 1), (1024, 1), (1024, 0)]
+    assert [_long_plan(lib, problems.benchmark_desc("cartpole", N=N))[1][:2] for N in (441, 442, 512)] == [(512, 1), (1024, 0), (1024, 0)]
+    assert [_long_plan(lib, problems.vdp_desc(N=N))[1][:2] for N in (257, 512, 513, 775, 776, 1024)] == [(512, 2), (512, 2), (1024, 2), (1024, 2), (1024, 1), (1024, 1)]
+    # no such kernel: short and too long horizons, the big-block family, extra edges (band / block-tridiagonal route), a null pointer
+    for d in (problems.unicycle_desc(N=256), problems.unicycle_desc(N=1025), problems.quad_desc(N=300), problems.planar_quadrotor_desc(N=300)):
+        assert _long_plan(lib, d)[0] != 0
+    assert b"" != lib.corbo_hip_last_error()
+    d = problems.unicycle_desc(N=300)
+    d.ctrl_dev = capi.CTRL_DEV_RATE
+    d.ctrl_dev_params[0] = d.ctrl_dev_params[1] = 0.3
+    assert _long_plan(lib, d)[0] != 0
+    assert lib.corbo_hip_long_factor_plan(None, None) != 0
+
+
 def test_the_oracle_refuses_what_the_reference_solver_refuses(oracle_mod):
     """LevenbergMarquardtSparse::solve returns Error for a problem with plain objective edges (levenberg_marquardt_sparse.cpp:48-55)."""
     d = problems.vdp_desc(N=8)

@@ -132,7 +132,8 @@ def test_plant_calls_need_a_plant_state():
     assert np.isfinite(s.plant_get_state()).all()
 
 
-@pytest.mark.parametrize("scenario,N,B,ocp_iterations", [("unicycle", 30, 16, 1), ("unicycle", 20, 5, 2), ("vdp", 20, 4, 1), ("dint", 20, 3, 1), ("quad", 10, 3, 1)])
+@pytest.mark.parametrize("scenario,N,B,ocp_iterations", [("unicycle", 30, 16, 1), ("unicycle", 20, 5, 2), ("vdp", 20, 4, 1), ("dint", 20, 3, 1), ("quad", 10, 3, 1),
+                                                         ("cartpole", 257, 3, 1)])   # the long-horizon kernels (separate launches per pass), nx = 4
 def test_closed_loop_call_equals_stepwise_sequence(scenario, N, B, ocp_iterations):
     """corbo_hip_closed_loop (everything enqueued, one synchronisation; the quadrotor family runs it step by step inside) is
     bit-identical to the same sequence driven through the single-step entry points; its logs are the states / applied controls."""

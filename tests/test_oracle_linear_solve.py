@@ -31,10 +31,65 @@ def first_iterations(oracle_mod):
 
 def test_table_covers_the_listed_paths():
     ids = {c.id for c in L.CASES}
-    assert len(ids) == len(L.CASES) >= 300
+    assert len(ids) == len(L.CASES) >= 413
     for route in ("cr", "long", "bt", "band", "big"):
         assert sum(L.BATCH for c in L.unique_inputs() if c.route == route and c.rejecting) >= 2, route   # at least two rejecting instances per route
     assert 2 <= L.BATCH <= 4
+
+
+def _long_plan(lib, d):
+    """(threads, workgroups per CU the LDS admits, non-diagonal weights) of corbo_hip_long_factor_plan: the instantiation class of factor_long_kernel"""
+    import ctypes as C
+    out = (C.c_int32 * 4)()
+    assert lib.corbo_hip_long_factor_plan(C.byref(d), C.byref(out)) == 0, lib.corbo_hip_last_error()
+    assert out[2] % 8 == 0 and (out[2] > 0) == (out[1] > 0) and out[2] + 128 + 64 <= 160 * 1024
+    return (out[0], out[1], out[3])
+
+
+def test_long_route_straddles_every_switch_of_the_launcher():
+    """The long-horizon cases against the launcher's own decision (corbo_hip_long_factor_plan; host only).  Per block shape (nx, nu, free dt) of the long route:
+    every instantiation class the plan returns for some N in 257 .. 1024 has a case, and wherever the class changes between N and N + 1 both horizons are
+    cases of that shape.  A layout change that moves a switch fails here: the table cannot silently stop straddling it."""
+    from control_box_rst_amd import capi
+    lib = capi.load()
+    shapes = {}   # (nx, nu, free dt, dense) -> {N: family}
+    for c in L.CASES:
+        if c.route == "long":
+            d = L.make_desc(c.family, c.N)
+            free = d.grid in (capi.GRID_FD_VARIABLE, capi.GRID_MS_VARIABLE)
+            shapes.setdefault((d.nx, d.nu, free, bool(d.weights_dense)), {})[c.N] = c.family
+    assert {k[:3] for k in shapes} == {(2, 1, False), (2, 1, True), (2, 2, False), (3, 1, False), (3, 1, True), (3, 2, False), (3, 3, False), (4, 1, False), (4, 1, True)}
+    for (nx, nu, free, dense), have in sorted(shapes.items()):
+        fam = next(iter(have.values()))
+        plan = {N: _long_plan(lib, L.make_desc(fam, N)) for N in range(257, 1025)}
+        reached = {plan[N] for N in have}
+        if dense:   # the non-diagonal instantiations: with and without the LDS carve where the shape reaches both in the table's families
+            assert reached <= set(plan.values()) and all(p[2] == 1 for p in reached), (nx, nu, free)
+            continue
+        assert reached == set(plan.values()), ((nx, nu, free), sorted(set(plan.values()) - reached))
+        for N in range(257, 1024):
+            if plan[N] != plan[N + 1]:
+                assert N in have and N + 1 in have, ((nx, nu, free), N, plan[N], plan[N + 1])
+    dense_classes = {_long_plan(lib, L.make_desc(c.family, c.N))[:2] for c in L.CASES if c.route == "long" and "+dense" in c.family}
+    assert dense_classes == {(1024, 2), (1024, 1), (1024, 0)}   # E with two / one workgroup per CU, F
+
+
+def test_long_factor_plan_switches():
+    """the switches of docs/measurements/r10.md, from the library: c (N | 1) + 130 doubles (+ nx (N | 1) with a free dt) + the LM state + 64 bytes against 160 KB"""
+    from control_box_rst_amd import capi
+    lib = capi.load()
+    two_one = ((1024, 2), (1024, 1))   # nx = 2: the same sixteen-wave instantiation, two | one workgroup per CU
+    want = {"vdp": {775: two_one}, "dint": {671: two_one}, "par2": {775: two_one},
+            "int3": {373: ((512, 2), (512, 1)), 751: ((1024, 1), (1024, 0))}, "par3": {373: ((512, 2), (512, 1)), 751: ((1024, 1), (1024, 0))},
+            "unicycle": {373: ((512, 2), (512, 1)), 751: ((1024, 1), (1024, 0))},
+            "int3t": {335: ((512, 2), (512, 1)), 677: ((1024, 1), (1024, 0))},
+            "cartpole": {441: ((512, 1), (1024, 0))}, "cartpolet": {405: ((512, 1), (1024, 0))}}
+    for fam, sw in want.items():
+        plan = {N: _long_plan(lib, L.make_desc(fam, N))[:2] for N in range(257, 1025)}
+        got = {N: (plan[N], plan[N + 1]) for N in range(257, 1024) if plan[N] != plan[N + 1] and N != 512}
+        assert got == sw, (fam, got)
+        assert plan[512][0] == 512 or plan[512][1] == 0, fam
+        assert plan[513][0] == 1024, fam
 
 
 def test_expected_damping_is_the_inner_loops_sum():
@@ -91,6 +146,7 @@ def test_weighted_handle_reference_solves_its_normal_equations(oracle_mod):
 #      defects show there like everywhere else (5e-4, 1e-3).  docs/measurements/r08.md.
 _SENSITIVITY_IDS = ("cr-unicyclems-N8-rej0", "cr-unicyclems-N33-rej0", "cr-unicycle-N100-rej0", "cr-int3t-N65",
                     "long-unicycle-N257-rej1", "long-unicycle-N257-rej2", "long-unicycle-N800", "long-dint-N513",
+                    "long-cartpole-N442", "long-par3-N752", "long-int3t-N336",
                     "bt-unicycle+rate-N6-rej0-bt_waves2", "bt-unicycle+rate-N12-rej0-bt_waves2", "bt-unicycle+rate-N40-rej0-bt_waves2", "bt-int3t+eqlin-N129-bt_waves2",
                     "band-cartpole+rate-N257-rej5", "band-unicycle+rate+eqlin+dense-N12", "band-vdp+eqlin-N300-route2-band_wide0",
                     "big-quad-N37-rej0-chain_variant2-reject_speculation0", "big-pquad-N65-chain_variant2", "big-quadt-N37-chain_variant2", "big-quad-N64-chain_variant2")
