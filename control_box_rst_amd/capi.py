@@ -48,7 +48,7 @@ class ProblemDesc(C.Structure):
         ("q_sqrt", C.c_double * 16), ("r_sqrt", C.c_double * 16), ("qf_sqrt", C.c_double * 16),
         ("constraint_integration", C.c_int32), ("stage_ineq_integral", C.c_int32), ("stage_eq", C.c_int32), ("ctrl_dev", C.c_int32),
         ("stage_eq_params", C.c_double * (MAX_NX + MAX_NU + 1)), ("ctrl_dev_params", C.c_double * MAX_NU),
-        ("stage_ineq_control", C.c_int32), ("reserved0", C.c_int32), ("ineq_control_params", C.c_double * 8),
+        ("stage_ineq_control", C.c_int32), ("stage_ineq_state_control", C.c_int32), ("ineq_control_params", C.c_double * 8),
     ]
 
 
@@ -116,8 +116,32 @@ EXPORTED_SYMBOLS = (
     "corbo_hip_device_count", "corbo_hip_shard_bounds", "corbo_hip_device_row_stride",
     "corbo_hip_set_references", "corbo_hip_set_reference_trajectory", "corbo_hip_hessian_nnz", "corbo_hip_hessian_structure", "corbo_hip_eval_hessians", "corbo_hip_eval_hessians_views", "corbo_hip_linear_form_structure", "corbo_hip_eval_linear_form", "corbo_hip_eval_objective_gradient",
     "corbo_hip_sizeof", "corbo_hip_set_previous_control", "corbo_hip_get_phase_cycles", "corbo_hip_create_routed", "corbo_hip_create_weighted", "corbo_hip_factor_route", "corbo_hip_stage_function_kind", "corbo_hip_eval_stage_function",
+    "corbo_hip_set_state_control_params", "corbo_hip_eval_stage_function_xu", "corbo_hip_stage_function_rows",
     "corbo_hip_long_factor_plan",
 )
+
+
+def stage_function_rows(fn_id: int) -> int:
+    """corbo_hip_stage_function_rows: rows of a registered user stage function (1 .. 4 for a state-control function, 1 for the other kinds), -1 = no such id."""
+    return int(load().corbo_hip_stage_function_rows(int(fn_id)))
+
+
+def eval_stage_function_xu(fn_id: int, x, u, prm):
+    """corbo_hip_eval_stage_function_xu: a state-control stage function on the host, through the header the kernels compile.  x [n][nx], u [n][nu], prm [<= 8]
+    -> [n][rows]."""
+    import numpy as np
+    lib = load()
+    x = np.ascontiguousarray(np.atleast_2d(np.asarray(x, np.float64)))
+    u = np.ascontiguousarray(np.atleast_2d(np.asarray(u, np.float64)))
+    p = np.zeros(8)
+    p[:len(prm)] = prm
+    rows = stage_function_rows(fn_id)
+    out = np.zeros((x.shape[0], max(rows, 1)))
+    dp = C.POINTER(C.c_double)
+    rc = lib.corbo_hip_eval_stage_function_xu(int(fn_id), x.shape[1], u.shape[1], x.shape[0], x.ctypes.data_as(dp), u.ctypes.data_as(dp), p.ctypes.data_as(dp), out.ctypes.data_as(dp))
+    if rc != 0:
+        raise ValueError(f"corbo_hip_eval_stage_function_xu: {lib.corbo_hip_last_error().decode()}")
+    return out
 
 
 def lib_path() -> str:
@@ -156,6 +180,10 @@ def load() -> C.CDLL:
     lib.corbo_hip_create.argtypes = [C.POINTER(ProblemDesc), C.c_int, C.c_int, C.POINTER(H)]
     lib.corbo_hip_stage_function_kind.argtypes = [C.c_int]
     lib.corbo_hip_eval_stage_function.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, dp]
+    if hasattr(lib, "corbo_hip_eval_stage_function_xu"):   # (an older build loaded through CORBO_HIP_LIB has no state-control stage functions)
+        lib.corbo_hip_stage_function_rows.argtypes = [C.c_int]
+        lib.corbo_hip_eval_stage_function_xu.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, dp, dp]
+        lib.corbo_hip_set_state_control_params.argtypes = [H, dp]
     lib.corbo_hip_create_routed.argtypes = [C.POINTER(ProblemDesc), C.c_int, C.c_int, C.c_uint32, C.POINTER(H)]
     if hasattr(lib, "corbo_hip_create_weighted"):
         lib.corbo_hip_create_weighted.argtypes = [C.POINTER(ProblemDesc), C.POINTER(WeightFactors), C.c_int, C.c_int, C.c_uint32, C.POINTER(H)]

@@ -287,7 +287,7 @@ struct corbo_hip_solver {
         p.batch = active; p.nvs = S.nvs; p.m = S.dims.m; p.nnz = S.dims.nnz; p.N = S.N; p.s = S.s; p.nx = S.nx; p.off_dt = S.off_dt; p.dt_free = S.dt_free;
         p.batch_total = batch + spare; p.xe0 = d_xe0; p.skip_jac = (d_xe0 && mode >= 2 && band.n == 0) ? 1 : 0;   // (band route: the factorisation reads the stored Jacobian)
         p.eq_row0 = S.eq_row0; p.ineq_row0 = S.ineq_row0;
-        p.ineq_stride = 1 + (S.desc.stage_ineq_control ? 1 : 0) + (S.desc.ctrl_dev ? S.nu : 0);   // (creation order per interval: state term, control term, control-deviation term)
+        p.ineq_stride = 1 + (S.desc.stage_ineq_control ? 1 : 0) + (S.desc.stage_ineq_state_control ? user_stage_rows(S.desc.stage_ineq_state_control) : 0) + (S.desc.ctrl_dev ? S.nu : 0);   // (creation order per interval: state term, control term, state-control term, control-deviation term)
         p.stage_cols = d_stage_cols; p.comp = d_comp; p.ineq_cols = d_ineq_cols;
         fill_dyn(p.mp.dyn);
         std::memcpy(p.mp.ineq, S.desc.ineq_params, sizeof(p.mp.ineq));
@@ -300,7 +300,7 @@ struct corbo_hip_solver {
         p.fin_eq_row0 = S.fin_eq_row0; p.fin_eq_dim = S.fin_eq_dim;
         p.xedges = d_xedges; p.n_xedges = (int32_t)S.xedges.size(); p.eq_stride = S.eq_stride; p.eq_defect_off = S.eq_defect_off;
         p.xtasks = reinterpret_cast<const int4*>(d_xtasks); p.n_xtasks = n_xtasks;
-        p.xparams = d_xparams; p.uprev = d_uprev;
+        p.xparams = d_xparams; p.uprev = d_uprev; p.ineq_xu_id = S.desc.stage_ineq_state_control;
         p.mp.wdense = d_wdense; p.mp.wdense_mask = d_wdense ? S.desc.weights_dense : 0;
         p.mp.fin_eq_mask = S.desc.final_eq ? (int32_t)S.desc.final_eq_mask : 0;
         p.fin_row = S.fin_row;
@@ -627,7 +627,7 @@ static int create_impl(const corbo_hip_problem_desc* desc, int batch, int device
             h->n_xtasks = (int32_t)(tasks.size() / 4);
             if (upload(tasks, &h->d_xtasks)) return CORBO_HIP_ERR_DEVICE;
         }
-        std::vector<double> xp(CORBO_HIP_MAX_NX + 2 * CORBO_HIP_MAX_NU + 2 + 8, 0.0);   // [stage_eq: a, b, c | ctrl_dev: r_max | control inequality: 8 parameters]
+        std::vector<double> xp(CORBO_HIP_MAX_NX + 2 * CORBO_HIP_MAX_NU + 2 + 8 + 8, 0.0);   // [stage_eq: a, b, c | ctrl_dev: r_max | control inequality: 8 parameters | state-control inequality: 8, corbo_hip_set_state_control_params]
         for (int i = 0; i < S.nx + S.nu + 1; ++i) xp[i] = S.desc.stage_eq_params[i];
         for (int i = 0; i < S.nu; ++i) xp[S.nx + S.nu + 1 + i] = S.desc.ctrl_dev_params[i];
         for (int i = 0; i < 8; ++i) xp[S.nx + 2 * S.nu + 1 + i] = S.desc.ineq_control_params[i];
@@ -647,7 +647,8 @@ static int create_impl(const corbo_hip_problem_desc* desc, int batch, int device
         const int max_rounds = bt_route_max_rounds(S.nx, S.nu, S.dt_free, S.N, (int)h->nnz_pad, (int)h->m_pad, S.nvs);
         BtTables bt;
         std::string why;
-        if (max_rounds > 0 && build_bt_tables(S, h->jmap, (int)h->nnz_pad, (int)h->m_pad, BT_THREADS, bt, &why) && bt.rounds <= max_rounds) {
+        const bool built = max_rounds > 0 && build_bt_tables(S, h->jmap, (int)h->nnz_pad, (int)h->m_pad, BT_THREADS, bt, &why);
+        if (built && bt.rounds <= max_rounds) {
             if (upload(bt.pairs, &h->d_bt_pairs) || upload(bt.off, &h->d_bt_off) || upload(bt.target, &h->d_bt_target)) return CORBO_HIP_ERR_DEVICE;
             h->bt_rounds = bt.rounds;
             bt_route = true;
@@ -657,6 +658,9 @@ static int create_impl(const corbo_hip_problem_desc* desc, int batch, int device
                 CREATE_TRY(hipMalloc((void**)&h->d_bt_snap, B * (size_t)h->bt_snap_stride * sizeof(double)));
             }
         }
+        else if (built && bt.rounds > max_rounds)   // block tridiagonal, but its product lists exceed what the kernel's LDS admits: every such handle says so at create
+            fprintf(stderr, "corbo_hip: extra edges of (nx %d, nu %d, N %d): %d list rounds > %d -- band factorisation instead of the block-tridiagonal route (corbo_hip_factor_route)\n",
+                    S.nx, S.nu, S.N, bt.rounds, max_rounds);
     }
     if (band_route) {
         if (!bt_route) h->force_split = true;   // separate launches: sweep_kernel (residual + Jacobian in HBM) + band_factor_kernel
@@ -917,6 +921,19 @@ try {
     }
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipMemcpy(h->d_uprev, up.data(), up.size() * sizeof(double), hipMemcpyHostToDevice));
+    return CORBO_HIP_OK;
+}
+ABI_CATCH
+
+int corbo_hip_set_state_control_params(corbo_hip_handle h, const double prm[8])
+try {
+    if (!h || !prm) return fail(CORBO_HIP_ERR_INVALID, "null argument");
+    if (!h->S.desc.stage_ineq_state_control || !h->d_xparams) return fail(CORBO_HIP_ERR_INVALID, "corbo_hip_set_state_control_params: the handle has no state-control stage function (stage_ineq_state_control)");
+    ON_DEVICE_OF(h);
+    DRAIN_ASYNC(h);
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    // (behind the control function's eight: the layout of SweepParams::xparams, written in corbo_hip_create)
+    HIP_TRY(hipMemcpy(h->d_xparams + h->S.nx + 2 * h->S.nu + 1 + 8, prm, 8 * sizeof(double), hipMemcpyHostToDevice));
     return CORBO_HIP_OK;
 }
 ABI_CATCH
@@ -2032,6 +2049,7 @@ int corbo_hip_hessian_nnz(const corbo_hip_problem_desc* desc, int lower_part_onl
 try {
     if (!desc || !nnz_out) return fail(CORBO_HIP_ERR_INVALID, "null argument");
     if (desc->stage_ineq_integral || desc->stage_eq || desc->ctrl_dev) return fail(CORBO_HIP_ERR_UNSUPPORTED, "Hessian-path operators with integral-form constraints / a control-deviation term: not built");
+    if (desc->stage_ineq_state_control) return fail(CORBO_HIP_ERR_UNSUPPORTED, "Hessian-path operators with a user state-control inequality (stage_ineq_state_control): not built");
     Structure S;
     std::string err = build_structure(*desc, S);
     if (!err.empty()) return fail(CORBO_HIP_ERR_INVALID, err);
@@ -2064,6 +2082,7 @@ ABI_CATCH
 static int hessian_common(corbo_hip_handle h, const HessianStructure*& Hout, bool lower, HessParams& hp)
 {
     if (!h->have_data) return fail(CORBO_HIP_ERR_STATE, "corbo_hip_set_instance_data must be called first");
+    if (h->S.desc.stage_ineq_state_control) return fail(CORBO_HIP_ERR_UNSUPPORTED, "Hessian-path operators with a user state-control inequality (stage_ineq_state_control): not built");
     if (h->S.has_extra()) return fail(CORBO_HIP_ERR_UNSUPPORTED, "Hessian-path operators with integral-form constraints / a control-deviation term: not built");
     // (their kernels read the descriptor-path table of 16 doubles per factor: never the diagonal, never a misread 12 x 12 factor)
     if (!h->S.wside.empty()) return fail(CORBO_HIP_ERR_UNSUPPORTED, "Hessian-path operators with non-diagonal weights around a big-block model (corbo_hip_create_weighted): not built");
@@ -2436,6 +2455,7 @@ try {
     if (!v || !prm || !out || n < 1 || dim < 1 || dim > CORBO_HIP_MAX_NX) return fail(CORBO_HIP_ERR_INVALID, "bad argument");
     const int kind = (id == CORBO_HIP_INEQ_BALL) ? 0 : corbo_hip_stage_function_kind(id);
     if (kind < 0) return fail(CORBO_HIP_ERR_INVALID, "not a registered stage function");
+    if (kind == 2) return fail(CORBO_HIP_ERR_INVALID, "a state-control function: corbo_hip_eval_stage_function_xu");
     switch (dim) {   // (the functions are templates on the vertex dimension, like the kernels instantiate them)
 #define CORBO_HIP_SF_DIM(D) case D: eval_stage_fn<D>(id, kind, n, v, prm, out); break;
         CORBO_HIP_SF_DIM(1) CORBO_HIP_SF_DIM(2) CORBO_HIP_SF_DIM(3) CORBO_HIP_SF_DIM(4) CORBO_HIP_SF_DIM(5) CORBO_HIP_SF_DIM(6)
@@ -2443,6 +2463,43 @@ try {
 #undef CORBO_HIP_SF_DIM
         default: return fail(CORBO_HIP_ERR_INVALID, "dimension out of range");
     }
+    return CORBO_HIP_OK;
+}
+ABI_CATCH
+
+int corbo_hip_stage_function_rows(int id) { return user_stage_rows(id); }
+
+int corbo_hip_eval_stage_function_xu(int id, int nx, int nu, int n, const double* x, const double* u, const double* prm, double* out)
+try {
+    if (!x || !u || !prm || !out || n < 1) return fail(CORBO_HIP_ERR_INVALID, "bad argument");
+    if (corbo_hip_stage_function_kind(id) != 2) return fail(CORBO_HIP_ERR_INVALID, "not a registered state-control stage function");
+    {   // dimensions the function accepts: the registry's own rule, as validate_desc applies it
+        bool ok = false;
+#if __has_include("stage_functions/_registry.inc")
+#define CORBO_HIP_USER_STAGE_XU(NAME, SLOT, ROWS_, NXMIN, NUMIN) if (id == CORBO_HIP_STAGE_FN_USER + SLOT) ok = nx >= NXMIN && nu >= NUMIN;
+#include "stage_functions/_registry.inc"
+#undef CORBO_HIP_USER_STAGE_XU
+#endif
+        if (!ok) return fail(CORBO_HIP_ERR_INVALID, "state-control stage function: nx / nu below the function's nx_min / nu_min");
+    }
+    const int rows = user_stage_rows(id);
+    bool done = false;
+    // (the functions are templates on the vertex dimensions, like the kernels instantiate them: every (nx, nu) a model table row or a user model can have)
+#define CORBO_HIP_SF_XU(NX_, NU_)                                                                                            \
+    if (!done && nx == NX_ && nu == NU_ && has_user_state_control_ineq<NX_, NU_>()) {                                         \
+        for (int p = 0; p < n; ++p) {                                                                                         \
+            double o[4] = {0.0, 0.0, 0.0, 0.0};                                                                               \
+            stage_ineq_state_control<NX_, NU_>(id, x + (size_t)p * NX_, u + (size_t)p * NU_, prm, o);                         \
+            for (int r = 0; r < rows; ++r) out[(size_t)p * rows + r] = o[r];                                                  \
+        }                                                                                                                     \
+        done = true;                                                                                                          \
+    }
+#define CORBO_HIP_SF_XU_ROW(NX_) CORBO_HIP_SF_XU(NX_, 1) CORBO_HIP_SF_XU(NX_, 2) CORBO_HIP_SF_XU(NX_, 3) CORBO_HIP_SF_XU(NX_, 4)
+    CORBO_HIP_SF_XU_ROW(1) CORBO_HIP_SF_XU_ROW(2) CORBO_HIP_SF_XU_ROW(3) CORBO_HIP_SF_XU_ROW(4) CORBO_HIP_SF_XU_ROW(5) CORBO_HIP_SF_XU_ROW(6)
+    CORBO_HIP_SF_XU_ROW(7) CORBO_HIP_SF_XU_ROW(8) CORBO_HIP_SF_XU_ROW(9) CORBO_HIP_SF_XU_ROW(10) CORBO_HIP_SF_XU_ROW(11) CORBO_HIP_SF_XU_ROW(12)
+#undef CORBO_HIP_SF_XU_ROW
+#undef CORBO_HIP_SF_XU
+    if (!done) return fail(CORBO_HIP_ERR_INVALID, "state-control stage function: nx in 1 .. 12 and nu in 1 .. 4");
     return CORBO_HIP_OK;
 }
 ABI_CATCH

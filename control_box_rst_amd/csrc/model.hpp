@@ -555,8 +555,8 @@ __host__ __device__ __forceinline__ double ineq_ball(const double* x, const doub
 }
 
 // ---- user stage functions dropped into csrc/stage_functions/ (generated include list and registry: __graft_entry__.build(); README.md there):
-//      StageFunction<slot>::value<NV>(vertex, prm), public id CORBO_HIP_STAGE_FN_USER + slot
-constexpr int CORBO_HIP_STAGE_FN_STATE_INEQ = 0, CORBO_HIP_STAGE_FN_CONTROL_INEQ = 1;
+//      StageFunction<slot>::value<NV>(vertex, prm) -- a state-control function: value<NX, NU>(x, u, prm, out[ROWS]) --, public id CORBO_HIP_STAGE_FN_USER + slot
+constexpr int CORBO_HIP_STAGE_FN_STATE_INEQ = 0, CORBO_HIP_STAGE_FN_CONTROL_INEQ = 1, CORBO_HIP_STAGE_FN_STATE_CONTROL_INEQ = 2;
 template <int SLOT> struct StageFunction;
 #if __has_include("stage_functions/_includes.inc")
 #include "stage_functions/_includes.inc"
@@ -606,6 +606,33 @@ __host__ __device__ __forceinline__ double stage_ineq_control(int id, const doub
     }
 #endif
     return 0.0;
+}
+// ... and their non-integral STATE-CONTROL term c(x_k, u_k), 1 to 4 rows (corbo_hip_problem_desc::stage_ineq_state_control); out[4]: the rows beyond the
+// function's own stay untouched
+template <int NX, int NU>
+__host__ __device__ __forceinline__ void stage_ineq_state_control(int id, const double* x, const double* u, const double* prm, double* out)
+{
+#if __has_include("stage_functions/_registry.inc")
+    switch (id - CORBO_HIP_STAGE_FN_USER) {
+#define CORBO_HIP_USER_STAGE_XU(NAME, SLOT, ROWS_, NXMIN, NUMIN) \
+        case SLOT: if constexpr (NX >= NXMIN && NU >= NUMIN) StageFunction<SLOT>::template value<NX, NU>(x, u, prm, out); break;
+#include "stage_functions/_registry.inc"
+#undef CORBO_HIP_USER_STAGE_XU
+        default: break;
+    }
+#endif
+}
+// is there a registered state-control function these dimensions can carry?  (the extra-edge sweep compiles the case only then)
+template <int NX, int NU>
+constexpr bool has_user_state_control_ineq()
+{
+    bool any = false;
+#if __has_include("stage_functions/_registry.inc")
+#define CORBO_HIP_USER_STAGE_XU(NAME, SLOT, ROWS_, NXMIN, NUMIN) any = any || (NX >= NXMIN && NU >= NUMIN);
+#include "stage_functions/_registry.inc"
+#undef CORBO_HIP_USER_STAGE_XU
+#endif
+    return any;
 }
 
 // ---- user models dropped into csrc/models/ (generated include list: __graft_entry__.build(); see models/README.md)

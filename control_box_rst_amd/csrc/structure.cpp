@@ -8,7 +8,8 @@
 
 namespace corbo_hip {
 
-// kind of a registered user stage function (csrc/stage_functions/_registry.inc): 0 state inequality, 1 control inequality; -1 = no such id (or nx below its nx_min)
+// kind of a registered user stage function (csrc/stage_functions/_registry.inc): 0 state inequality, 1 control inequality, 2 state-control inequality;
+// -1 = no such id (or nx below its nx_min)
 static int user_stage_kind(int id, int nx)
 {
     (void)nx;
@@ -19,6 +20,32 @@ static int user_stage_kind(int id, int nx)
 #endif
     (void)id;
     return -1;
+}
+
+int user_stage_rows(int id)
+{
+#if __has_include("stage_functions/_registry.inc")
+#define CORBO_HIP_USER_STAGE_XU(NAME, SLOT, ROWS_, NXMIN, NUMIN) if (id == CORBO_HIP_STAGE_FN_USER + SLOT) return ROWS_;
+#include "stage_functions/_registry.inc"
+#undef CORBO_HIP_USER_STAGE_XU
+#define CORBO_HIP_USER_STAGE(NAME, SLOT, KIND_, NXMIN) if (id == CORBO_HIP_STAGE_FN_USER + SLOT) return 1;
+#include "stage_functions/_registry.inc"
+#undef CORBO_HIP_USER_STAGE
+#endif
+    (void)id;
+    return -1;
+}
+
+// a registered state-control function (kind 2) these dimensions can carry?
+static bool user_stage_xu_ok(int id, int nx, int nu)
+{
+#if __has_include("stage_functions/_registry.inc")
+#define CORBO_HIP_USER_STAGE_XU(NAME, SLOT, ROWS_, NXMIN, NUMIN) if (id == CORBO_HIP_STAGE_FN_USER + SLOT) return nx >= NXMIN && nu >= NUMIN;
+#include "stage_functions/_registry.inc"
+#undef CORBO_HIP_USER_STAGE_XU
+#endif
+    (void)id; (void)nx; (void)nu;
+    return false;
 }
 
 static bool finite_bound(double lb, double ub) { return lb > -CORBO_HIP_INF || ub < CORBO_HIP_INF; }  // vector_vertex.h:174-184
@@ -83,6 +110,9 @@ std::string validate_desc(const corbo_hip_problem_desc& d)
     if (!(d.stage_ineq >= CORBO_HIP_INEQ_NONE && d.stage_ineq <= CORBO_HIP_INEQ_BALL) && user_stage_kind(d.stage_ineq, d.nx) != 0) return "unknown stage inequality (user state functions: csrc/stage_functions/, kind=state_ineq, nx >= its nx_min)";
     if (d.stage_ineq_control != 0 && user_stage_kind(d.stage_ineq_control, d.nx) != 1) return "stage_ineq_control: not a registered control_ineq function (csrc/stage_functions/)";
     if (d.stage_ineq_control != 0 && (d.cost_nonlsq || d.cost_integral)) return "stage_ineq_control: Levenberg-Marquardt path only";
+    if (d.stage_ineq_state_control != 0 && !user_stage_xu_ok(d.stage_ineq_state_control, d.nx, d.nu))
+        return "stage_ineq_state_control: not a registered state_control_ineq function (csrc/stage_functions/) with nx >= its nx_min and nu >= its nu_min";
+    if (d.stage_ineq_state_control != 0 && (d.cost_nonlsq || d.cost_integral)) return "stage_ineq_state_control: Levenberg-Marquardt path only";
     if (d.stage_ineq == CORBO_HIP_INEQ_BALL && d.nx < 3) return "ball inequality needs nx >= 3";
     if (d.final_ineq < CORBO_HIP_FINAL_INEQ_NONE || d.final_ineq > CORBO_HIP_FINAL_INEQ_TERMINAL_BALL) return "unknown final-stage inequality";
     if (d.final_ineq != CORBO_HIP_FINAL_INEQ_NONE && d.nx > 4 && !big_family_dims(d.nx, d.nu)) return "terminal ball: families with nx <= 4, and the big-block family";
@@ -116,7 +146,7 @@ std::string validate_desc(const corbo_hip_problem_desc& d)
     }
     if (!(d.dt_ref > 0)) return "dt_ref must be > 0";
     {   // integral-form constraints / control-deviation term (user stage functions of the reference)
-        const bool any = d.stage_ineq_integral || d.stage_eq || d.ctrl_dev || d.stage_ineq_control;
+        const bool any = d.stage_ineq_integral || d.stage_eq || d.ctrl_dev || d.stage_ineq_control || d.stage_ineq_state_control;
         if (d.constraint_integration < 0 || d.constraint_integration > 2) return "constraint_integration: 0, 1 (trapezoidal rule) or 2 (left sum)";
         if (d.stage_ineq_integral != 0 && d.stage_ineq_integral != 1) return "stage_ineq_integral must be 0 or 1";
         if (d.stage_ineq_integral && (d.stage_ineq == CORBO_HIP_INEQ_NONE || !d.constraint_integration)) return "stage_ineq_integral needs a stage inequality and a constraint_integration rule";
@@ -202,6 +232,7 @@ std::string build_structure(const corbo_hip_problem_desc& d, Structure& S)
         //  term, then control-deviation term, nlp_functions.cpp:70-131 --, then the integral equality / dynamics edges, then the integral inequality)
         if (d.stage_ineq != CORBO_HIP_INEQ_NONE && !d.stage_ineq_integral) ineq.push_back({EK_STAGE_INEQ, k, 1, 2});
         if (d.stage_ineq_control) ineq.push_back({EK_U_INEQ, k, 1, 2});   // the control term's edge on u_k (nlp_functions.cpp:82-89)
+        if (d.stage_ineq_state_control) ineq.push_back({EK_XU_INEQ, k, user_stage_rows(d.stage_ineq_state_control), 2});   // the state-control term's edge on (x_k, u_k) (nlp_functions.cpp:109-115)
         if (d.ctrl_dev) ineq.push_back({EK_CTRL_DEV, k, nu, 2});
         if (d.stage_eq && d.constraint_integration == 2) eq.push_back({EK_XI_EQ_LEFT, k, 1, 1});
         eq.push_back({EK_DEFECT, k, (d.stage_eq && d.constraint_integration == 1) ? nx + 1 : nx, 1});
@@ -258,6 +289,7 @@ std::string build_structure(const corbo_hip_problem_desc& d, Structure& S)
                 v[2] = {S.off_dt, 1}; return 3;
             case EK_XI_EQ_LEFT: v[0] = {k * s, nx}; v[1] = {k * s + nx, nu}; v[2] = {S.off_dt, 1}; return 3;
             case EK_U_INEQ: v[0] = {k * s + nx, nu}; return 1;
+            case EK_XU_INEQ: v[0] = {k * s, nx}; v[1] = {k * s + nx, nu}; return 2;
             case EK_CTRL_DEV:   // (u_k, u_prev, dt_prev): finite_differences_grid.cpp:51-53; the last one on (u_ref, u_{N-2}, dt), :149
                 if (k == N) { v[0] = {-2, nu}; v[1] = {(N - 2) * s + nx, nu}; v[2] = {S.off_dt, 1}; return 3; }
                 v[0] = {k * s + nx, nu};
@@ -288,7 +320,7 @@ std::string build_structure(const corbo_hip_problem_desc& d, Structure& S)
     };
     auto add_list = [&](const std::vector<E>& list) {
         for (const E& e : list) {
-            if (e.kind == EK_XI_INEQ || e.kind == EK_XI_EQ_LEFT || e.kind == EK_CTRL_DEV || e.kind == EK_U_INEQ) { add_extra(e); continue; }
+            if (e.kind == EK_XI_INEQ || e.kind == EK_XI_EQ_LEFT || e.kind == EK_CTRL_DEV || e.kind == EK_U_INEQ || e.kind == EK_XU_INEQ) { add_extra(e); continue; }
             if (e.kind == EK_DEFECT && e.dim > nx) {   // TrapezoidalIntegralEqualityDynamicsEdge: the appended row as an XEdge over the dynamics edge's blocks
                 XEdge x{};
                 XV v[4];
@@ -392,8 +424,8 @@ std::string validate_weight_factors(const corbo_hip_problem_desc& d, const corbo
         for (int j = 0; j < i; ++j)
             if ((w.mask & 2) && w.r_sqrt[i * d.nu + j] != 0.0) return "r_sqrt must be upper triangular";
     if (d.nx > 4) {   // what the big-block family's DENSE instantiations cover (kernels.hip, big_stage_kernel WD)
-        if (d.ctrl_dev || d.stage_ineq_integral || d.stage_eq || d.stage_ineq_control)
-            return "non-diagonal weights around a big-block model with extra edges (control-deviation term, integral-form constraints, a user control inequality): "
+        if (d.ctrl_dev || d.stage_ineq_integral || d.stage_eq || d.stage_ineq_control || d.stage_ineq_state_control)
+            return "non-diagonal weights around a big-block model with extra edges (control-deviation term, integral-form constraints, a user control / state-control inequality): "
                    "the band route has no dense-weight instantiation for nx > 4";
         if (d.grid == CORBO_HIP_GRID_FD_VARIABLE || d.grid == CORBO_HIP_GRID_MS_VARIABLE)
             return "non-diagonal weights around a big-block model on a free-dt grid (MultipleShootingVariableGrid / FiniteDifferencesVariableGrid): fixed-dt grids only";

@@ -50,7 +50,8 @@ enum EdgeKind : int32_t {
     EK_XI_EQ_LEFT = 18,     // LeftSumEqualityEdge (x_k, u_k, dt)
     EK_XI_EQ_ROW  = 19,     // the integral row the trapezoidal rule appends to the dynamics edge (TrapezoidalIntegralEqualityDynamicsEdge: dimension nx + 1)
     EK_CTRL_DEV   = 20,     // TernaryVectorScalarVertexEdge<computeNonIntegralControlDeviationTerm> (u_k, u_prev, dt_prev)
-    EK_U_INEQ     = 21      // UnaryVectorVertexEdge<computeNonIntegralControlTerm> on u_k: a user stage inequality's control term (csrc/stage_functions/)
+    EK_U_INEQ     = 21,     // UnaryVectorVertexEdge<computeNonIntegralControlTerm> on u_k: a user stage inequality's control term (csrc/stage_functions/)
+    EK_XU_INEQ    = 22      // BinaryVectorVertexEdge<computeNonIntegralStateControlTerm> on (x_k, u_k): its state-control term, 1 to 4 rows (nlp_functions.cpp:109-115)
 };
 
 // One "extra" edge (the kinds above), evaluated by a lane of the sweep kernel's generic loop (sweep_body, XE): attached vertices with their storage
@@ -154,6 +155,8 @@ bool build_bt_tables(const Structure& S, const std::vector<int32_t>& jmap, int n
 
 // returns "" on success, otherwise an error text
 std::string validate_desc(const corbo_hip_problem_desc& d);
+// rows of a registered state-control stage function (csrc/stage_functions/, kind 2), 1 for the functions of the other kinds, -1 = no such id
+int user_stage_rows(int id);
 std::string build_structure(const corbo_hip_problem_desc& d, Structure& out);
 // corbo_hip_create_weighted: the factors beside the descriptor (checked before any HIP call).  nx <= 4: the descriptor path's structure (factors moved
 // into q_sqrt / r_sqrt / qf_sqrt, weights_dense = mask); big-block family: Structure::wside

@@ -117,6 +117,17 @@ def hessian_path_cost_form(d: ProblemDesc, integral: str = "") -> ProblemDesc:
     return d
 
 
+def with_state_control_ineq(d: ProblemDesc, slot: int, params) -> ProblemDesc:
+    """Add the stage inequalities' non-integral state-control term c(x_k, u_k) -- the user function registered in `slot` of csrc/stage_functions/
+    (kind=state_control_ineq; shipped: 2 = drive_power, 3 = input_envelope) -- to a descriptor.  Its up to eight parameters are no field of the
+    descriptor: they ride on the Python object (`d.state_control_params`), and BatchedLevenbergMarquardt hands them to
+    corbo_hip_set_state_control_params when it creates the handle."""
+    prm = [float(v) for v in params] + [0.0] * 8
+    d.stage_ineq_state_control = capi.STAGE_FN_USER + int(slot)
+    d.state_control_params = tuple(prm[:8])
+    return d
+
+
 def min_time_quadratic(d: ProblemDesc, q, r, only_last_n=0) -> ProblemDesc:
     """Turn a time-optimal descriptor (free dt, MinimumTime) into the reference's MinTimeQuadratic(Q, R, integral=False, lsq=True)
     (hybrid_cost.h:189-303): the quadratic form's state and control terms next to the minimum-time term; only_last_n > 0: on the

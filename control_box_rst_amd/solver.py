@@ -93,7 +93,7 @@ def init_trajectory(desc: ProblemDesc, x0, xf) -> np.ndarray:
 class BatchedLevenbergMarquardt:
     """LevenbergMarquardtSparse for `batch` independent instances of one hypergraph structure, on one MI355X."""
 
-    def __init__(self, desc: ProblemDesc, batch: int, device: int = 0, route: int = 0, weights=None):
+    def __init__(self, desc: ProblemDesc, batch: int, device: int = 0, route: int = 0, weights=None, state_control_params=None):
         self.lib = capi.load()
         self.desc = desc
         self.batch = int(batch)
@@ -112,6 +112,18 @@ class BatchedLevenbergMarquardt:
         else:
             rc = self.lib.corbo_hip_create(C.byref(desc), self.batch, self.device, C.byref(self._h))
         self._check(rc, "corbo_hip_create")
+        # state_control_params: the parameters of the descriptor's state-control stage function (stage_ineq_state_control) -- given here, or attached to
+        # the descriptor by problems.with_state_control_ineq; they live beside the descriptor, whose size is fixed
+        if state_control_params is None:
+            state_control_params = getattr(desc, "state_control_params", None)
+        if desc.stage_ineq_state_control and state_control_params is not None:
+            self.set_state_control_params(state_control_params)
+
+    def set_state_control_params(self, params):
+        """corbo_hip_set_state_control_params: the (up to eight) parameters of the handle's state-control stage function, shared by every instance."""
+        p = np.zeros(8)
+        p[:len(params)] = params
+        self._check(self.lib.corbo_hip_set_state_control_params(self._h, _dp(p)), "corbo_hip_set_state_control_params")
 
     # -- reference setters ------------------------------------------------------------------------------------------
     def setIterations(self, iterations: int):

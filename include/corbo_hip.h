@@ -114,8 +114,11 @@ typedef enum corbo_hip_stage_ineq {
 /* User stage functions: a `StageFunction<slot>` specialisation dropped into control_box_rst_amd/csrc/stage_functions/ (README.md there) is registered by
  * the build under the id CORBO_HIP_STAGE_FN_USER + slot, slot = 0 .. 15 -- the device-side counterpart of a user's own corbo::StageInequalityConstraint
  * subclass (stage_functions.h:276-310).  kind = state_ineq: its non-integral STATE term c(x_k) (dimension 1), named in `stage_ineq`, parameters
- * `ineq_params`; kind = control_ineq: its non-integral CONTROL term c(u_k) (dimension 1), named in `stage_ineq_control`, parameters `ineq_control_params`.
- * Shipped examples: slot 0 = tilt cone x[6]^2 + x[7]^2 - alpha^2 (state), slot 1 = input magnitude |u|^2 - r^2 (control). */
+ * `ineq_params`; kind = control_ineq: its non-integral CONTROL term c(u_k) (dimension 1), named in `stage_ineq_control`, parameters `ineq_control_params`;
+ * kind = state_control_ineq: its non-integral STATE-CONTROL term c(x_k, u_k) (1 to 4 rows, `value<NX, NU>(x, u, prm, out)`), named in
+ * `stage_ineq_state_control`, parameters through corbo_hip_set_state_control_params.
+ * Shipped examples: slot 0 = tilt cone x[6]^2 + x[7]^2 - alpha^2 (state), slot 1 = input magnitude |u|^2 - r^2 (control), slot 2 = drive power
+ * (u[0] x[2])^2 - P^2 (state-control, 1 row), slot 3 = input envelope |u_i| <= a_i + b_i x[2]^2, i = 0, 1 (state-control, 4 rows). */
 #define CORBO_HIP_STAGE_FN_USER 1000
 
 typedef enum corbo_hip_final_ineq {
@@ -231,7 +234,12 @@ typedef struct corbo_hip_problem_desc {
      * control-deviation edge (nlp_functions.cpp:82-89).  An edge on u_k alone; every family and grid on the Levenberg-Marquardt path (handles with it take
      * the extra-edge routes like the control-deviation term does). */
     int32_t stage_ineq_control;
-    int32_t reserved0;
+    /* The stage inequalities' non-integral STATE-CONTROL term (getNonIntegralStateControlTermDimension = 1 .. 4): 0 = none, else CORBO_HIP_STAGE_FN_USER + slot of a
+     * registered `state_control_ineq` function -- one BinaryVectorVertexEdge on (x_k, u_k) per interval with the function's rows, created behind the control term's
+     * edge and in front of the control-deviation edge (nlp_functions.cpp:109-115).  Same limits as the other extra edges: Levenberg-Marquardt path, 3 <= N <= 1024,
+     * shooting integrators up to Runge-Kutta 4, no non-diagonal weights for nx > 4.  Its eight parameters are no part of the descriptor (whose size is fixed):
+     * corbo_hip_set_state_control_params, zeros until then.  (Was `reserved0`: same offset, 0 = every descriptor as before.) */
+    int32_t stage_ineq_state_control;
     double ineq_control_params[8];
 } corbo_hip_problem_desc;
 
@@ -323,7 +331,7 @@ int corbo_hip_create(const corbo_hip_problem_desc* desc, int batch, int device, 
 /* The same with an explicit choice of the factorisation ROUTE where a descriptor has two (A/B measurements and the cross-route parity tests;
  * the library reads no environment variable).  `route` = OR of:
  *   CORBO_HIP_ROUTE_FREE_DT_BAND  a free dt around a big-block model through the general band factorisation instead of the stage / chain kernels' border column
- *   CORBO_HIP_ROUTE_XE_BAND       extra edges (control-deviation term, integral-form constraint edges, a user control inequality) of the small-block families
+ *   CORBO_HIP_ROUTE_XE_BAND       extra edges (control-deviation term, integral-form constraint edges, a user control / state-control inequality) of the small-block families
  *                                 up to 256 grid points through the general band factorisation instead of the block-tridiagonal route (one launch per solve)
  * 0 = what corbo_hip_create chooses.  A flag that does not apply to the descriptor is ignored. */
 #define CORBO_HIP_ROUTE_FREE_DT_BAND 1u
@@ -376,6 +384,11 @@ int corbo_hip_set_instance_data(corbo_hip_handle h, const double* x, const doubl
  * control-deviation edge of interval 0 sees (corbo_hip_problem_desc::ctrl_dev).  u_prev [batch][nu], dt_prev [batch]; NULL = zeros resp. the
  * descriptor's dt_ref (the reference's defaults, structured_optimal_control_problem.cpp:67-71). */
 int corbo_hip_set_previous_control(corbo_hip_handle h, const double* u_prev, const double* dt_prev);
+
+/* The eight parameters of the handle's state-control stage function (corbo_hip_problem_desc::stage_ineq_state_control; `prm` of its
+ * StageFunction<slot>::value), shared by every instance; zeros after corbo_hip_create.  They live beside the descriptor because its size is part of the
+ * ABI.  Takes effect with the next solve / eval (a solve in flight is drained first).  CORBO_HIP_ERR_INVALID on a handle without such a term. */
+int corbo_hip_set_state_control_params(corbo_hip_handle h, const double prm[8]);
 
 
 /* Time-varying state reference (what ReferenceTrajectoryInterface::getReferenceCached(k) hands the cost and final-stage terms,
@@ -638,12 +651,17 @@ int corbo_hip_set_profiling(corbo_hip_handle h, int enable);
  * descriptor names (the adapter's recogniser matches user systems against the library's plug-in models with it). */
 int corbo_hip_eval_dynamics(const corbo_hip_problem_desc* desc, int n, const double* x, const double* u, double* f);
 
-/* User stage functions (csrc/stage_functions/): kind of a registered id -- 0 state inequality, 1 control inequality, -1 = not registered -- and the value
- * c(v, prm) of such a function (or of CORBO_HIP_INEQ_BALL) at n points, evaluated on the HOST by the very template the kernels compile: v [n][dim], out [n].
+/* User stage functions (csrc/stage_functions/): kind of a registered id -- 0 state inequality, 1 control inequality, 2 state-control inequality, -1 = not
+ * registered -- and the value c(v, prm) of a function of kind 0 / 1 (or of CORBO_HIP_INEQ_BALL) at n points, evaluated on the HOST by the very template the kernels compile: v [n][dim], out [n].
  * Lets a caller check that a stage-function object it holds is the function an id names (the adapter's recogniser matches a graph's inequality edges with it,
  * like corbo_hip_eval_dynamics for a dynamics object).  Needs no GPU. */
 int corbo_hip_stage_function_kind(int id);
 int corbo_hip_eval_stage_function(int id, int dim, int n, const double* v, const double* prm, double* out);
+/* A registered state-control function (kind 2) on the host, through the header the kernels compile: x [n][nx], u [n][nu], prm [8] -> out [n][rows].
+ * corbo_hip_stage_function_rows: its row count (1 .. 4); 1 for a function of the other kinds, -1 = no such id.
+ * CORBO_HIP_ERR_INVALID: not such a function, nx / nu below its nx_min / nu_min.  Needs no GPU. */
+int corbo_hip_eval_stage_function_xu(int id, int nx, int nu, int n, const double* x, const double* u, const double* prm, double* out);
+int corbo_hip_stage_function_rows(int id);
 
 /* Diagnostics and test hooks of a handle (nothing here is read from the environment):
  *   "pass_limit"        value > 0: the run-to-completion kernel gives up after `value` LM passes per instance instead of 4096
