@@ -1494,7 +1494,7 @@ static int warm_start_from(corbo_hip_handle h, const double* x0_dev_visible, int
     p.shift = (shift != 0 && !S.dt_free) ? 1 : 0;   // variable grids never shift (finite_differences_variable_grid.h:77)
     p.x = h->d_x; p.x0new = x0_dev_visible; p.xref = h->d_xref;
     if (p.batch == 0) return CORBO_HIP_OK;
-    launch_warm_start(p, h->stream);
+    if (!launch_warm_start(p, h->stream)) return fail(CORBO_HIP_ERR_UNSUPPORTED, "warm start: one trajectory row does not fit the 160 KB of LDS of a compute unit");
     HIP_TRY(hipGetLastError());
     return CORBO_HIP_OK;
 }
@@ -1811,7 +1811,7 @@ try {
     p.n_src = A.N; p.nvs_src = A.nvs; p.n_dst = B.N; p.nvs_dst = B.nvs;
     p.x_src = src->d_x; p.x_dst = dst->d_x; p.xref_src = src->d_xref; p.xref_dst = dst->d_xref;
     p.src_index = tmp.p; p.dst_index = tmp.p + count;
-    launch_resample(p, dst->stream);
+    if (!launch_resample(p, dst->stream)) return fail(CORBO_HIP_ERR_UNSUPPORTED, "corbo_hip_resample_into: one source trajectory row does not fit the 160 KB of LDS of a compute unit");
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(dst->stream));
     return CORBO_HIP_OK;

@@ -6209,9 +6209,13 @@ void launch_upload_instance(const UploadParams& p, hipStream_t stream)
     hipLaunchKernelGGL(upload_instance_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p);
 }
 
-void launch_resample(const ResampleParams& p, hipStream_t stream)
+bool launch_resample(const ResampleParams& p, hipStream_t stream)
 {
-    hipLaunchKernelGGL(resample_kernel, dim3(p.pairs), dim3(256), sizeof(double) * (size_t)p.nvs_src, stream, p);
+    const size_t lds = sizeof(double) * (size_t)p.nvs_src;   // the staged source row: above 64 KB from N = 513 on at nx + nu = 16
+    if (lds > (size_t)160 * 1024) return false;
+    set_max_dynamic_lds(resample_kernel, 160 * 1024);
+    hipLaunchKernelGGL(resample_kernel, dim3(p.pairs), dim3(256), lds, stream, p);
+    return true;
 }
 
 __global__ __launch_bounds__(256) void gather_dt_kernel(const double* __restrict__ x, double* __restrict__ out, int nvs, int off_dt, int batch)
@@ -6225,10 +6229,13 @@ void launch_gather_dt(const double* x, double* out, int nvs, int off_dt, int bat
     hipLaunchKernelGGL(gather_dt_kernel, dim3((batch + 255) / 256), dim3(256), 0, stream, x, out, nvs, off_dt, batch);
 }
 
-void launch_warm_start(const WarmStartParams& p, hipStream_t stream)
+bool launch_warm_start(const WarmStartParams& p, hipStream_t stream)
 {
-    const size_t lds = sizeof(double) * ((size_t)p.nvs + 24);
+    const size_t lds = sizeof(double) * ((size_t)p.nvs + 24);   // the new row + the distances: above 64 KB from N = 511 on at nx + nu = 16
+    if (lds > (size_t)160 * 1024) return false;
+    set_max_dynamic_lds(warm_start_kernel, 160 * 1024);
     hipLaunchKernelGGL(warm_start_kernel, dim3(p.batch), dim3(256), lds, stream, p);
+    return true;
 }
 
 size_t sweep_lds_bytes(const SweepParams& p, int nc)

@@ -245,7 +245,8 @@ struct WarmStartParams {
     const double* x0new;  // [batch][CORBO_HIP_MAX_NX]
     const double* xref;   // [batch][CORBO_HIP_MAX_NX]
 };
-void launch_warm_start(const WarmStartParams& p, hipStream_t stream);
+// false (nothing launched): the row does not fit a CU's 160 KB of LDS
+bool launch_warm_start(const WarmStartParams& p, hipStream_t stream);
 // FullDiscretizationGridBase::resampleTrajectory (full_discretization_grid_base.cpp:397-474) between two batches of free-dt grids with
 // N_src / N_dst grid points: pair q takes instance src_index[q] of the source arrays to instance dst_index[q] of the destination arrays
 struct ResampleParams {
@@ -258,7 +259,8 @@ struct ResampleParams {
     const int32_t* src_index; // [pairs] (device-visible)
     const int32_t* dst_index;
 };
-void launch_resample(const ResampleParams& p, hipStream_t stream);
+// false (nothing launched): the source row does not fit a CU's 160 KB of LDS
+bool launch_resample(const ResampleParams& p, hipStream_t stream);
 // dst (and dst2, may be null) = src, `doubles` values (even), as a kernel on `stream` (no copy engine: see kernels.hip)
 // (src may be pinned, device-visible HOST memory: the upload of a staged array is then the same kernel, no DMA engine either)
 void launch_copy_rows(const double* src, double* dst, double* dst2, size_t doubles, hipStream_t stream, double* dst3 = nullptr);

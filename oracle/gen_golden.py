@@ -125,6 +125,32 @@ def adapt():
         print(name, [st["n_seq"] for st in d["steps"]])
 
 
+def gridupdate():
+    """The grid updates alone (iters=0 after the first step), at shapes the mpc_* / mpc_dint_adapt_* fixtures do not reach: resampling chains of the
+    nx = 3 / 6 / 12 time-optimal families on both variable grids, and moving-horizon sequences whose measured state is x_jump of the previous solution
+    (jump / meas_noise of ref_driver's mpc mode), so that warmStartShifting moves by several samples, by N - 2, and hits findNearestState's cap of 20."""
+    chain = dict(vargrid=1, steps=4, iters0=6, iters=0, shift=0, ocp_iters=3)
+    jump = dict(steps=3, iters=0, shift=1)
+    for name, kv in [
+        ("mpc_int3_adapt_single_init", dict(chain, scenario="int3", N=20, dt=0.06, adapt="single", nmax=80, hyst=0.02)),
+        ("mpc_pquad_ms_adapt_single_init", dict(chain, scenario="pquad", N=12, adapt="single", nmax=40, hyst=0.02)),   # shrinks to n = 4
+        ("mpc_pquad_fd_adapt_aggressive_init", dict(chain, scenario="pquad", grid="fd", N=12, adapt="aggressive", nmax=40, hyst=0.05, adapt_first=1)),   # 12 -> 40
+        ("mpc_quad_adapt_single_init", dict(chain, scenario="quad", N=8, adapt="single", nmax=40, hyst=0.02)),   # shrinks to n = 2
+        ("mpc_unicycle_jump7_init", dict(jump, scenario="unicycle", N=30, jump=7, meas_noise=0.001)),
+        ("mpc_unicycle_jump25_init", dict(jump, scenario="unicycle", N=30, jump=25, meas_noise=0.001)),       # num_shift 20: the cap
+        ("mpc_unicycle_n12_jump10_init", dict(jump, scenario="unicycle", N=12, jump=10, meas_noise=0.0001)),  # num_shift N - 2
+        ("mpc_vdp_jump3_init", dict(jump, scenario="vdp", jump=3, meas_noise=0.001)),
+        ("mpc_pquad_jump5_init", dict(jump, scenario="pquad", N=24, jump=5, meas_noise=0.0001, iters0=4)),
+        ("mpc_quad_jump2_init", dict(jump, scenario="quad", N=10, jump=2, meas_noise=0.0001, iters0=4)),
+    ]:
+        d = run("mpc", **kv)
+        path = os.path.join(OUT, f"{name}.json")
+        with open(path, "w") as f:
+            json.dump(d, f, separators=(",", ":"))
+        assert os.path.getsize(path) < 40 * 1024, (name, os.path.getsize(path))
+        print(name, os.path.getsize(path), "bytes, n_seq", [st["n_seq"] for st in d["steps"]])
+
+
 def hess():
     """Operators of the exact-Hessian path at a generic point: computeSparseHessians{Structure,Values} (full and
     lower part, seeded multipliers) and the two-side-bounded linear form with its bounds, from the genuine reference
@@ -812,6 +838,8 @@ def main():
         return fullsize()
     if len(sys.argv) > 1 and sys.argv[1] == "adapt":
         return adapt()
+    if len(sys.argv) > 1 and sys.argv[1] == "gridupdate":
+        return gridupdate()
     if len(sys.argv) > 1 and sys.argv[1] == "mtq":
         return mtq()
     if len(sys.argv) > 1 and sys.argv[1] == "nonlsq":
@@ -929,6 +957,7 @@ def main():
             json.dump(d, f, separators=(",", ":"))
         print(name, [round(st["chi2"], 6) for st in d["steps"]])
     adapt()
+    gridupdate()
 
     # closed loops with the reference's own SimulatedPlant: plant.output -> compute(new_run) -> plant.control, the
     # plant integrating the OCP's dynamics with explicit Euler (its default) or RK4, plus a deterministic state disturbance

@@ -1189,6 +1189,11 @@ static int mpc(const Scenario& s, std::map<std::string, std::string>& kv)
     // ocp_iters=K: K compute() calls per step like PredictiveController::step (predictive_controller.cpp:46-80), new_run only for the
     // first -- the calls in which a variable grid adapts its resolution (adaptGrid skips new runs unless adapt_first)
     const int ocp_iters = kv.count("ocp_iters") ? atoi(kv["ocp_iters"].c_str()) : 1;
+    // jump=K: the next measurement is x_K of the solution (default x_1), meas_noise=A the amplitude of its disturbance (default 0.01): with K > 1
+    // and a small A the warm start shifts by several samples (findNearestState, full_discretization_grid_base.cpp:285-317)
+    const int jump          = kv.count("jump") ? atoi(kv["jump"].c_str()) : 1;
+    const double meas_noise = kv.count("meas_noise") ? atof(kv["meas_noise"].c_str()) : 0.01;
+    if (jump < 0 || jump > s.N - 1) { fprintf(stderr, "jump must be in 0 .. N-1\n"); return 4; }
     Built b = build(s, iters0);
     if (shift && b.grid) b.grid->setWarmStart(true);
     // ShootingGridBase: the same shifting (shooting_grid_base.cpp:99-113,292-352).  Without warm start a shooting grid re-initialises its
@@ -1205,6 +1210,7 @@ static int mpc(const Scenario& s, std::map<std::string, std::string>& kv)
     if (s.lin_a.size()) { printVec("lin_a", s.lin_a); printVec("lin_b", s.lin_b); }
     printVec("xf", s.xf);
     if (kv.count("plant_a")) printf("\"plant_a\": %.17g,\n", atof(kv["plant_a"].c_str()));
+    if (kv.count("jump") || kv.count("meas_noise")) printf("\"jump\": %d, \"meas_noise\": %.17g,\n", jump, meas_noise);
     printf("\"steps\": [\n");
     Eigen::VectorXd x0 = s.x0;
     for (int st = 0; st < steps; ++st)
@@ -1224,7 +1230,7 @@ static int mpc(const Scenario& s, std::map<std::string, std::string>& kv)
         printVec("x0", x0);
         printVec("vertex", v, false);
         printf("}%s\n", st + 1 < steps ? "," : "");
-        for (int i = 0; i < s.nx; ++i) x0[i] = v[s.nx + s.nu + i] + 0.01 * std::sin(1.0 + st + 0.5 * i);   // x_1 + disturbance
+        for (int i = 0; i < s.nx; ++i) x0[i] = v[jump * (s.nx + s.nu) + i] + meas_noise * std::sin(1.0 + st + 0.5 * i);   // x_jump + disturbance
     }
     printf("]\n}\n");
     return 0;

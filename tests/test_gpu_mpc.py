@@ -22,8 +22,10 @@ def _built():
                                         ("int3", 17), ("vdp", 3), ("unicycle", 256), ("quad", 5),
                                         ("unicycle", 257), ("cartpole", 1024), ("par3", 1024)])   # beyond 256 grid points: every block width
 def test_warm_start_bit_exact_vs_oracle(oracle_mod, scenario, N):
-    """Random resident trajectories; the measured state of instance b is stored state (b mod 5) plus a small offset, so shifts of
-    0 .. 4 samples (and the `same start` early exit) all occur in one batch; with and without shifting."""
+    """Random resident trajectories; the measured state of instance b is stored state (b mod 5) plus a small offset.  findNearestState stops at the
+    first sample that is not nearer, and the distances along a random trajectory do not fall monotonically: over the 13 cases these inputs reach
+    shifts of 0 .. 3 samples (65 x 0, 45 x 1, 18 x 2, 2 x 3 of 130 instances) and the `same start` early exit; with and without shifting.  Every
+    larger shift, the look-ahead cap and num_shift = N - 2 are in tests/test_gpu_grid_update.py."""
     mk, w = problems.SCENARIOS[scenario]
     d = mk(N=N)
     B = 10
