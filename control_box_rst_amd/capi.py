@@ -122,12 +122,12 @@ EXPORTED_SYMBOLS = (
 
 
 def stage_function_rows(fn_id: int) -> int:
-    """corbo_hip_stage_function_rows: rows of a registered user stage function (1 .. 4 for a state-control function, 1 for the other kinds), -1 = no such id."""
+    """corbo_hip_stage_function_rows: rows of a registered user stage function (1 .. 4 for a state-control inequality / equality, 1 for the other kinds), -1 = no such id."""
     return int(load().corbo_hip_stage_function_rows(int(fn_id)))
 
 
 def eval_stage_function_xu(fn_id: int, x, u, prm):
-    """corbo_hip_eval_stage_function_xu: a state-control stage function on the host, through the header the kernels compile.  x [n][nx], u [n][nu], prm [<= 8]
+    """corbo_hip_eval_stage_function_xu: a state-control stage function (inequality, kind 2, or equality, kind 3) on the host, through the header the kernels compile.  x [n][nx], u [n][nu], prm [<= 8]
     -> [n][rows]."""
     import numpy as np
     lib = load()

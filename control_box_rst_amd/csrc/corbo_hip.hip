@@ -300,7 +300,7 @@ struct corbo_hip_solver {
         p.fin_eq_row0 = S.fin_eq_row0; p.fin_eq_dim = S.fin_eq_dim;
         p.xedges = d_xedges; p.n_xedges = (int32_t)S.xedges.size(); p.eq_stride = S.eq_stride; p.eq_defect_off = S.eq_defect_off;
         p.xtasks = reinterpret_cast<const int4*>(d_xtasks); p.n_xtasks = n_xtasks;
-        p.xparams = d_xparams; p.uprev = d_uprev; p.ineq_xu_id = S.desc.stage_ineq_state_control;
+        p.xparams = d_xparams; p.uprev = d_uprev; p.ineq_xu_id = S.desc.stage_ineq_state_control; p.eq_xu_id = stage_eq_is_user(S.desc) ? S.desc.stage_eq : 0;
         p.mp.wdense = d_wdense; p.mp.wdense_mask = d_wdense ? S.desc.weights_dense : 0;
         p.mp.fin_eq_mask = S.desc.final_eq ? (int32_t)S.desc.final_eq_mask : 0;
         p.fin_row = S.fin_row;
@@ -627,8 +627,13 @@ static int create_impl(const corbo_hip_problem_desc* desc, int batch, int device
             h->n_xtasks = (int32_t)(tasks.size() / 4);
             if (upload(tasks, &h->d_xtasks)) return CORBO_HIP_ERR_DEVICE;
         }
-        std::vector<double> xp(CORBO_HIP_MAX_NX + 2 * CORBO_HIP_MAX_NU + 2 + 8 + 8, 0.0);   // [stage_eq: a, b, c | ctrl_dev: r_max | control inequality: 8 parameters | state-control inequality: 8, corbo_hip_set_state_control_params]
-        for (int i = 0; i < S.nx + S.nu + 1; ++i) xp[i] = S.desc.stage_eq_params[i];
+        // [stage_eq (linear integral row): a, b, c | ctrl_dev: r_max | control inequality: 8 parameters | state-control inequality: 8, corbo_hip_set_state_control_params |
+        //  state-control equality: 8, stage_eq_params[0..7]]
+        std::vector<double> xp(CORBO_HIP_MAX_NX + 2 * CORBO_HIP_MAX_NU + 2 + 8 + 8 + 8, 0.0);
+        if (stage_eq_is_user(S.desc))
+            for (int i = 0; i < 8; ++i) xp[S.nx + 2 * S.nu + 1 + 16 + i] = S.desc.stage_eq_params[i];
+        else
+            for (int i = 0; i < S.nx + S.nu + 1; ++i) xp[i] = S.desc.stage_eq_params[i];
         for (int i = 0; i < S.nu; ++i) xp[S.nx + S.nu + 1 + i] = S.desc.ctrl_dev_params[i];
         for (int i = 0; i < 8; ++i) xp[S.nx + 2 * S.nu + 1 + i] = S.desc.ineq_control_params[i];
         CREATE_TRY(hipMalloc((void**)&h->d_xparams, xp.size() * sizeof(double)));
@@ -2048,7 +2053,8 @@ struct DevBuf {   // scratch device buffer of one call
 int corbo_hip_hessian_nnz(const corbo_hip_problem_desc* desc, int lower_part_only, int32_t* nnz_out)
 try {
     if (!desc || !nnz_out) return fail(CORBO_HIP_ERR_INVALID, "null argument");
-    if (desc->stage_ineq_integral || desc->stage_eq || desc->ctrl_dev) return fail(CORBO_HIP_ERR_UNSUPPORTED, "Hessian-path operators with integral-form constraints / a control-deviation term: not built");
+    if (desc->stage_eq >= CORBO_HIP_STAGE_FN_USER) return fail(CORBO_HIP_ERR_UNSUPPORTED, "Hessian-path operators with a user state-control equality (stage_eq): not built");
+    if (desc->stage_ineq_integral || desc->stage_eq == CORBO_HIP_STAGE_EQ_LINEAR || desc->ctrl_dev) return fail(CORBO_HIP_ERR_UNSUPPORTED, "Hessian-path operators with integral-form constraints / a control-deviation term: not built");
     if (desc->stage_ineq_state_control) return fail(CORBO_HIP_ERR_UNSUPPORTED, "Hessian-path operators with a user state-control inequality (stage_ineq_state_control): not built");
     Structure S;
     std::string err = build_structure(*desc, S);
@@ -2083,6 +2089,7 @@ static int hessian_common(corbo_hip_handle h, const HessianStructure*& Hout, boo
 {
     if (!h->have_data) return fail(CORBO_HIP_ERR_STATE, "corbo_hip_set_instance_data must be called first");
     if (h->S.desc.stage_ineq_state_control) return fail(CORBO_HIP_ERR_UNSUPPORTED, "Hessian-path operators with a user state-control inequality (stage_ineq_state_control): not built");
+    if (stage_eq_is_user(h->S.desc)) return fail(CORBO_HIP_ERR_UNSUPPORTED, "Hessian-path operators with a user state-control equality (stage_eq): not built");
     if (h->S.has_extra()) return fail(CORBO_HIP_ERR_UNSUPPORTED, "Hessian-path operators with integral-form constraints / a control-deviation term: not built");
     // (their kernels read the descriptor-path table of 16 doubles per factor: never the diagonal, never a misread 12 x 12 factor)
     if (!h->S.wside.empty()) return fail(CORBO_HIP_ERR_UNSUPPORTED, "Hessian-path operators with non-diagonal weights around a big-block model (corbo_hip_create_weighted): not built");
@@ -2455,7 +2462,7 @@ try {
     if (!v || !prm || !out || n < 1 || dim < 1 || dim > CORBO_HIP_MAX_NX) return fail(CORBO_HIP_ERR_INVALID, "bad argument");
     const int kind = (id == CORBO_HIP_INEQ_BALL) ? 0 : corbo_hip_stage_function_kind(id);
     if (kind < 0) return fail(CORBO_HIP_ERR_INVALID, "not a registered stage function");
-    if (kind == 2) return fail(CORBO_HIP_ERR_INVALID, "a state-control function: corbo_hip_eval_stage_function_xu");
+    if (kind >= 2) return fail(CORBO_HIP_ERR_INVALID, "a state-control function: corbo_hip_eval_stage_function_xu");
     switch (dim) {   // (the functions are templates on the vertex dimension, like the kernels instantiate them)
 #define CORBO_HIP_SF_DIM(D) case D: eval_stage_fn<D>(id, kind, n, v, prm, out); break;
         CORBO_HIP_SF_DIM(1) CORBO_HIP_SF_DIM(2) CORBO_HIP_SF_DIM(3) CORBO_HIP_SF_DIM(4) CORBO_HIP_SF_DIM(5) CORBO_HIP_SF_DIM(6)
@@ -2472,12 +2479,16 @@ int corbo_hip_stage_function_rows(int id) { return user_stage_rows(id); }
 int corbo_hip_eval_stage_function_xu(int id, int nx, int nu, int n, const double* x, const double* u, const double* prm, double* out)
 try {
     if (!x || !u || !prm || !out || n < 1) return fail(CORBO_HIP_ERR_INVALID, "bad argument");
-    if (corbo_hip_stage_function_kind(id) != 2) return fail(CORBO_HIP_ERR_INVALID, "not a registered state-control stage function");
+    const int kind = corbo_hip_stage_function_kind(id);
+    if (kind != 2 && kind != 3) return fail(CORBO_HIP_ERR_INVALID, "not a registered state-control stage function");
+    const bool is_eq = kind == 3;   // (a state_control_eq function: the other list of the registry, the other dispatcher)
     {   // dimensions the function accepts: the registry's own rule, as validate_desc applies it
         bool ok = false;
 #if __has_include("stage_functions/_registry.inc")
 #define CORBO_HIP_USER_STAGE_XU(NAME, SLOT, ROWS_, NXMIN, NUMIN) if (id == CORBO_HIP_STAGE_FN_USER + SLOT) ok = nx >= NXMIN && nu >= NUMIN;
+#define CORBO_HIP_USER_STAGE_XU_EQ(NAME, SLOT, ROWS_, NXMIN, NUMIN) if (id == CORBO_HIP_STAGE_FN_USER + SLOT) ok = nx >= NXMIN && nu >= NUMIN;
 #include "stage_functions/_registry.inc"
+#undef CORBO_HIP_USER_STAGE_XU_EQ
 #undef CORBO_HIP_USER_STAGE_XU
 #endif
         if (!ok) return fail(CORBO_HIP_ERR_INVALID, "state-control stage function: nx / nu below the function's nx_min / nu_min");
@@ -2486,10 +2497,11 @@ try {
     bool done = false;
     // (the functions are templates on the vertex dimensions, like the kernels instantiate them: every (nx, nu) a model table row or a user model can have)
 #define CORBO_HIP_SF_XU(NX_, NU_)                                                                                            \
-    if (!done && nx == NX_ && nu == NU_ && has_user_state_control_ineq<NX_, NU_>()) {                                         \
+    if (!done && nx == NX_ && nu == NU_ && (is_eq ? has_user_state_control_eq<NX_, NU_>() : has_user_state_control_ineq<NX_, NU_>())) { \
         for (int p = 0; p < n; ++p) {                                                                                         \
             double o[4] = {0.0, 0.0, 0.0, 0.0};                                                                               \
-            stage_ineq_state_control<NX_, NU_>(id, x + (size_t)p * NX_, u + (size_t)p * NU_, prm, o);                         \
+            if (is_eq) stage_eq_state_control<NX_, NU_>(id, x + (size_t)p * NX_, u + (size_t)p * NU_, prm, o);                \
+            else stage_ineq_state_control<NX_, NU_>(id, x + (size_t)p * NX_, u + (size_t)p * NU_, prm, o);                    \
             for (int r = 0; r < rows; ++r) out[(size_t)p * rows + r] = o[r];                                                  \
         }                                                                                                                     \
         done = true;                                                                                                          \

@@ -255,7 +255,7 @@ __device__ __forceinline__ double dense_weight_row(const double* U, int c, int d
 // in the reference's operation order (finite_differences_collocation_edges.h:149-459: 0.5 * dt * (c1 + c2) resp. c1, then *= dt; the plug-in
 // stage functions as oracle/ref_driver.cpp states them).  loc[vi][c]: component c of attached vertex vi.
 template <int NX, int NU>
-__device__ __forceinline__ void xedge_values(const XEdge& xe, const double (&loc)[4][(NX > NU ? NX : NU)], const double* xp, const ModelParams& mp, const int xu_id, double (&out)[4])
+__device__ __forceinline__ void xedge_values(const XEdge& xe, const double (&loc)[4][(NX > NU ? NX : NU)], const double* xp, const ModelParams& mp, const int xu_id, const int xu_eq_id, double (&out)[4])
 {
     constexpr int MC = (NX > NU) ? NX : NU;   // components of the widest attached vertex
     auto lin = [&](const double (&x)[MC], const double (&u)[MC]) {   // a^T x + b^T u - c, summed left to right
@@ -297,6 +297,16 @@ __device__ __forceinline__ void xedge_values(const XEdge& xe, const double (&loc
 #pragma unroll
                 for (int i = 0; i < NU; ++i) u[i] = loc[1][i];
                 stage_ineq_state_control<NX, NU>(xu_id, x, u, xp + NX + 2 * NU + 1 + 8, out);
+            }
+            break;
+        case EK_XU_EQ:   // the stage equalities' non-integral state-control term e(x_k, u_k), 1 to 4 rows: a user function, parameters behind the inequality's
+            if constexpr (has_user_state_control_eq<NX, NU>()) {
+                double x[NX], u[NU];
+#pragma unroll
+                for (int i = 0; i < NX; ++i) x[i] = loc[0][i];
+#pragma unroll
+                for (int i = 0; i < NU; ++i) u[i] = loc[1][i];
+                stage_eq_state_control<NX, NU>(xu_eq_id, x, u, xp + NX + 2 * NU + 1 + 16, out);
             }
             break;
         default:   // EK_CTRL_DEV: ((u_k - u_prev) / dt_prev)^2 - r_max^2 per control
@@ -847,7 +857,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams& p, const int mode,
             const XEdge xe = p.xedges[i];
             double loc[4][XMC], out[4];
             xe_load(xe, loc);
-            xedge_values<NX, NU>(xe, loc, p.xparams, p.mp, p.ineq_xu_id, out);
+            xedge_values<NX, NU>(xe, loc, p.xparams, p.mp, p.ineq_xu_id, p.eq_xu_id, out);
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 if (j < xe.dim) {
@@ -1249,7 +1259,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams& p, const int mode,
                 const XEdge xe = p.xedges[tk.x];
                 double loc[4][XMC], f0[4], v2[4], v1[4];
                 xe_load(xe, loc);
-                xedge_values<NX, NU>(xe, loc, p.xparams, p.mp, p.ineq_xu_id, f0);
+                xedge_values<NX, NU>(xe, loc, p.xparams, p.mp, p.ineq_xu_id, p.eq_xu_id, f0);
                 double keep = 0.0;
 #pragma unroll
                 for (int vi = 0; vi < 4; ++vi)
@@ -1260,12 +1270,12 @@ __device__ __forceinline__ void sweep_body(const SweepParams& p, const int mode,
                 for (int vi = 0; vi < 4; ++vi)
 #pragma unroll
                     for (int c = 0; c < XMC; ++c) loc[vi][c] = (vi == tk.y && c == tk.z) ? a : loc[vi][c];
-                xedge_values<NX, NU>(xe, loc, p.xparams, p.mp, p.ineq_xu_id, v2);
+                xedge_values<NX, NU>(xe, loc, p.xparams, p.mp, p.ineq_xu_id, p.eq_xu_id, v2);
 #pragma unroll
                 for (int vi = 0; vi < 4; ++vi)
 #pragma unroll
                     for (int c = 0; c < XMC; ++c) loc[vi][c] = (vi == tk.y && c == tk.z) ? b : loc[vi][c];
-                xedge_values<NX, NU>(xe, loc, p.xparams, p.mp, p.ineq_xu_id, v1);
+                xedge_values<NX, NU>(xe, loc, p.xparams, p.mp, p.ineq_xu_id, p.eq_xu_id, v1);
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
                     if (j < xe.dim) {
@@ -1280,7 +1290,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams& p, const int mode,
             const XEdge xe = p.xedges[i];
             double loc[4][XMC], f0[4];
             xe_load(xe, loc);
-            xedge_values<NX, NU>(xe, loc, p.xparams, p.mp, p.ineq_xu_id, f0);
+            xedge_values<NX, NU>(xe, loc, p.xparams, p.mp, p.ineq_xu_id, p.eq_xu_id, f0);
 #pragma unroll
             for (int vi = 0; vi < 4; ++vi) {
                 if (vi >= xe.nverts || xe.joff[vi] < 0) continue;
@@ -1291,9 +1301,9 @@ __device__ __forceinline__ void sweep_body(const SweepParams& p, const int mode,
                     const double keep = loc[vi][c];
                     double v2[4], v1[4];
                     loc[vi][c] += delta;
-                    xedge_values<NX, NU>(xe, loc, p.xparams, p.mp, p.ineq_xu_id, v2);
+                    xedge_values<NX, NU>(xe, loc, p.xparams, p.mp, p.ineq_xu_id, p.eq_xu_id, v2);
                     loc[vi][c] += neg2delta;
-                    xedge_values<NX, NU>(xe, loc, p.xparams, p.mp, p.ineq_xu_id, v1);
+                    xedge_values<NX, NU>(xe, loc, p.xparams, p.mp, p.ineq_xu_id, p.eq_xu_id, v1);
                     loc[vi][c] = keep;
 #pragma unroll
                     for (int j = 0; j < 4; ++j)

@@ -55,8 +55,9 @@ struct SweepParams {
     int32_t ineq_xu_id;                 // corbo_hip_problem_desc::stage_ineq_state_control (model.hpp stage_ineq_state_control), read by the EK_XU_INEQ edges only (sits in what was padding)
     const int4* xtasks;                 // or null: one entry per Jacobian COLUMN of the extra edges -- (edge, attached vertex, component, first Jacobian value of the column)
     int32_t n_xtasks;
-    int32_t eq_stride, eq_defect_off;   // equality rows per interval and the defect's row inside them (nx, 0 without integral equality rows)
-    const double* xparams;              // [stage_eq: a (nx), b (nu), c | ctrl_dev: r_max (nu) | control inequality: 8 | state-control inequality: 8]
+    int32_t eq_stride, eq_defect_off;   // equality rows per interval and the defect's row inside them (nx, 0 without integral equality rows / a user state-control equality)
+    int32_t eq_xu_id;                   // corbo_hip_problem_desc::stage_eq when it names a user state-control equality (model.hpp stage_eq_state_control), else 0; read by the EK_XU_EQ edges only (sits in what was padding)
+    const double* xparams;              // [stage_eq (linear integral row): a (nx), b (nu), c | ctrl_dev: r_max (nu) | control inequality: 8 | state-control inequality: 8 | state-control equality: 8]
     const double* uprev;                // [batch_total][CORBO_HIP_MAX_NU + 1]: previously applied control, its age (corbo_hip_set_previous_control)
     int32_t mode;       // 0 = residual only, 1 = residual + Jacobian, 2 = LM init, 3 = LM trial step
     int32_t iterations; // LM: outer iteration count

@@ -555,8 +555,8 @@ __host__ __device__ __forceinline__ double ineq_ball(const double* x, const doub
 }
 
 // ---- user stage functions dropped into csrc/stage_functions/ (generated include list and registry: __graft_entry__.build(); README.md there):
-//      StageFunction<slot>::value<NV>(vertex, prm) -- a state-control function: value<NX, NU>(x, u, prm, out[ROWS]) --, public id CORBO_HIP_STAGE_FN_USER + slot
-constexpr int CORBO_HIP_STAGE_FN_STATE_INEQ = 0, CORBO_HIP_STAGE_FN_CONTROL_INEQ = 1, CORBO_HIP_STAGE_FN_STATE_CONTROL_INEQ = 2;
+//      StageFunction<slot>::value<NV>(vertex, prm) -- a state-control function (inequality or equality): value<NX, NU>(x, u, prm, out[ROWS]) --, public id CORBO_HIP_STAGE_FN_USER + slot
+constexpr int CORBO_HIP_STAGE_FN_STATE_INEQ = 0, CORBO_HIP_STAGE_FN_CONTROL_INEQ = 1, CORBO_HIP_STAGE_FN_STATE_CONTROL_INEQ = 2, CORBO_HIP_STAGE_FN_STATE_CONTROL_EQ = 3;
 template <int SLOT> struct StageFunction;
 #if __has_include("stage_functions/_includes.inc")
 #include "stage_functions/_includes.inc"
@@ -631,6 +631,32 @@ constexpr bool has_user_state_control_ineq()
 #define CORBO_HIP_USER_STAGE_XU(NAME, SLOT, ROWS_, NXMIN, NUMIN) any = any || (NX >= NXMIN && NU >= NUMIN);
 #include "stage_functions/_registry.inc"
 #undef CORBO_HIP_USER_STAGE_XU
+#endif
+    return any;
+}
+// ... and the stage EQUALITIES' non-integral state-control term e(x_k, u_k) = 0, 1 to 4 rows (corbo_hip_problem_desc::stage_eq = CORBO_HIP_STAGE_FN_USER + slot);
+// out[4]: the rows beyond the function's own stay untouched
+template <int NX, int NU>
+__host__ __device__ __forceinline__ void stage_eq_state_control(int id, const double* x, const double* u, const double* prm, double* out)
+{
+#if __has_include("stage_functions/_registry.inc")
+    switch (id - CORBO_HIP_STAGE_FN_USER) {
+#define CORBO_HIP_USER_STAGE_XU_EQ(NAME, SLOT, ROWS_, NXMIN, NUMIN) \
+        case SLOT: if constexpr (NX >= NXMIN && NU >= NUMIN) StageFunction<SLOT>::template value<NX, NU>(x, u, prm, out); break;
+#include "stage_functions/_registry.inc"
+#undef CORBO_HIP_USER_STAGE_XU_EQ
+        default: break;
+    }
+#endif
+}
+template <int NX, int NU>
+constexpr bool has_user_state_control_eq()
+{
+    bool any = false;
+#if __has_include("stage_functions/_registry.inc")
+#define CORBO_HIP_USER_STAGE_XU_EQ(NAME, SLOT, ROWS_, NXMIN, NUMIN) any = any || (NX >= NXMIN && NU >= NUMIN);
+#include "stage_functions/_registry.inc"
+#undef CORBO_HIP_USER_STAGE_XU_EQ
 #endif
     return any;
 }

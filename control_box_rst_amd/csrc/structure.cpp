@@ -8,8 +8,8 @@
 
 namespace corbo_hip {
 
-// kind of a registered user stage function (csrc/stage_functions/_registry.inc): 0 state inequality, 1 control inequality, 2 state-control inequality;
-// -1 = no such id (or nx below its nx_min)
+// kind of a registered user stage function (csrc/stage_functions/_registry.inc): 0 state inequality, 1 control inequality, 2 state-control inequality,
+// 3 state-control equality; -1 = no such id (or nx below its nx_min)
 static int user_stage_kind(int id, int nx)
 {
     (void)nx;
@@ -28,6 +28,9 @@ int user_stage_rows(int id)
 #define CORBO_HIP_USER_STAGE_XU(NAME, SLOT, ROWS_, NXMIN, NUMIN) if (id == CORBO_HIP_STAGE_FN_USER + SLOT) return ROWS_;
 #include "stage_functions/_registry.inc"
 #undef CORBO_HIP_USER_STAGE_XU
+#define CORBO_HIP_USER_STAGE_XU_EQ(NAME, SLOT, ROWS_, NXMIN, NUMIN) if (id == CORBO_HIP_STAGE_FN_USER + SLOT) return ROWS_;
+#include "stage_functions/_registry.inc"
+#undef CORBO_HIP_USER_STAGE_XU_EQ
 #define CORBO_HIP_USER_STAGE(NAME, SLOT, KIND_, NXMIN) if (id == CORBO_HIP_STAGE_FN_USER + SLOT) return 1;
 #include "stage_functions/_registry.inc"
 #undef CORBO_HIP_USER_STAGE
@@ -46,6 +49,18 @@ static bool user_stage_xu_ok(int id, int nx, int nu)
 #endif
     (void)id; (void)nx; (void)nu;
     return false;
+}
+
+// a registered state-control EQUALITY (kind 3): 1 = these dimensions can carry it, 0 = nx / nu below its minima, -1 = no such function
+static int user_stage_xu_eq_ok(int id, int nx, int nu)
+{
+#if __has_include("stage_functions/_registry.inc")
+#define CORBO_HIP_USER_STAGE_XU_EQ(NAME, SLOT, ROWS_, NXMIN, NUMIN) if (id == CORBO_HIP_STAGE_FN_USER + SLOT) return (nx >= NXMIN && nu >= NUMIN) ? 1 : 0;
+#include "stage_functions/_registry.inc"
+#undef CORBO_HIP_USER_STAGE_XU_EQ
+#endif
+    (void)id; (void)nx; (void)nu;
+    return -1;
 }
 
 static bool finite_bound(double lb, double ub) { return lb > -CORBO_HIP_INF || ub < CORBO_HIP_INF; }  // vector_vertex.h:174-184
@@ -107,6 +122,9 @@ std::string validate_desc(const corbo_hip_problem_desc& d)
         return "cost_integral on the MultipleShootingGrid (MultipleShootingEdgeSingleControl): diagonal Q / R, no stage inequality, nx <= 8";
     if (d.quad_first_interval < 0 || d.quad_first_interval > d.N - 1) return "quad_first_interval out of range";
     if (d.quad_first_interval != 0 && d.stage_cost != CORBO_HIP_COST_MIN_TIME_QUADRATIC_LSQ) return "quad_first_interval: MinTimeQuadratic only";
+    for (const int id : {d.stage_ineq, d.stage_ineq_control, d.stage_ineq_state_control})   // (asked without the nx_min rule: the kind decides the field)
+        if (user_stage_xu_eq_ok(id, CORBO_HIP_MAX_NX, CORBO_HIP_MAX_NU) >= 0)
+            return "a state_control_eq function (csrc/stage_functions/) is a stage EQUALITY: name it in stage_eq, not in stage_ineq / stage_ineq_control / stage_ineq_state_control";
     if (!(d.stage_ineq >= CORBO_HIP_INEQ_NONE && d.stage_ineq <= CORBO_HIP_INEQ_BALL) && user_stage_kind(d.stage_ineq, d.nx) != 0) return "unknown stage inequality (user state functions: csrc/stage_functions/, kind=state_ineq, nx >= its nx_min)";
     if (d.stage_ineq_control != 0 && user_stage_kind(d.stage_ineq_control, d.nx) != 1) return "stage_ineq_control: not a registered control_ineq function (csrc/stage_functions/)";
     if (d.stage_ineq_control != 0 && (d.cost_nonlsq || d.cost_integral)) return "stage_ineq_control: Levenberg-Marquardt path only";
@@ -150,15 +168,26 @@ std::string validate_desc(const corbo_hip_problem_desc& d)
         if (d.constraint_integration < 0 || d.constraint_integration > 2) return "constraint_integration: 0, 1 (trapezoidal rule) or 2 (left sum)";
         if (d.stage_ineq_integral != 0 && d.stage_ineq_integral != 1) return "stage_ineq_integral must be 0 or 1";
         if (d.stage_ineq_integral && (d.stage_ineq == CORBO_HIP_INEQ_NONE || !d.constraint_integration)) return "stage_ineq_integral needs a stage inequality and a constraint_integration rule";
-        if (d.stage_eq != CORBO_HIP_STAGE_EQ_NONE && d.stage_eq != CORBO_HIP_STAGE_EQ_LINEAR) return "unknown stage equality";
-        if (d.stage_eq && !d.constraint_integration) return "stage_eq (integral form) needs a constraint_integration rule";
+        const bool eq_lin = d.stage_eq == CORBO_HIP_STAGE_EQ_LINEAR, eq_user = stage_eq_is_user(d);   // the two uses of stage_eq exclude each other
+        if (eq_user) {   // a user state-control equality e(x_k, u_k) = 0: a non-integral term, every grid creates its edge (multiple_shooting_grid.cpp:65-68)
+            const int ok = user_stage_xu_eq_ok(d.stage_eq, d.nx, d.nu);
+            if (ok < 0)
+                return user_stage_rows(d.stage_eq) > 0 ? "stage_eq: a registered stage function of another kind (stage_eq takes kind=state_control_eq, csrc/stage_functions/)"
+                                                       : "unknown stage equality (stage_eq: CORBO_HIP_STAGE_EQ_LINEAR, or CORBO_HIP_STAGE_FN_USER + slot of a registered state_control_eq function, csrc/stage_functions/)";
+            if (ok == 0) return "stage_eq: nx / nu below the state_control_eq function's nx_min / nu_min";
+            if (d.cost_nonlsq || d.cost_integral) return "stage_eq (user state-control equality): Levenberg-Marquardt path only";
+            if (d.shooting_integrator >= 5) return "stage_eq (user state-control equality): shooting integrators up to Runge-Kutta 4";
+            if (d.N < 3 || d.N > 1024) return "stage_eq (user state-control equality): 3 <= N <= 1024";
+        }
+        else if (d.stage_eq != CORBO_HIP_STAGE_EQ_NONE && !eq_lin) return "unknown stage equality";
+        if (eq_lin && !d.constraint_integration) return "stage_eq (integral form) needs a constraint_integration rule";
         if (d.ctrl_dev != CORBO_HIP_CTRL_DEV_NONE && d.ctrl_dev != CORBO_HIP_CTRL_DEV_RATE) return "unknown control-deviation term";
         if (any) {
             // The integral-form edges are classes of the finite-differences grids (finite_differences_collocation_edges.h:149-459); on the shooting grids
             // integral terms make the interval a MIXED edge (multiple_shooting_grid.cpp:70-77), which lives on the Hessian path (cost_integral).  The
             // control-deviation term is a non-integral term: every grid creates it (multiple_shooting_grid.cpp:62, 193-197).
             const bool fd_grid = (d.grid == CORBO_HIP_GRID_FD || d.grid == CORBO_HIP_GRID_FD_VARIABLE);
-            if (!fd_grid && (d.stage_ineq_integral || d.stage_eq)) return "integral-form constraint edges: FiniteDifferencesGrid and FiniteDifferencesVariableGrid (the shooting grids take the control-deviation term only)";
+            if (!fd_grid && (d.stage_ineq_integral || eq_lin)) return "integral-form constraint edges: FiniteDifferencesGrid and FiniteDifferencesVariableGrid (the shooting grids take the control-deviation term only)";
             if (d.cost_nonlsq || d.cost_integral) return "integral-form constraints / control-deviation term: Levenberg-Marquardt path (least-squares costs) only";
             if (d.nx > 4 && !big_family_dims(d.nx, d.nu)) return "integral-form constraints / control-deviation term: families with nx <= 4, and the big-block family";
             if (d.N < 3 || d.N > 1024) return "integral-form constraints / control-deviation term: 3 <= N <= 1024";
@@ -218,6 +247,8 @@ std::string build_structure(const corbo_hip_problem_desc& d, Structure& S)
     // ---- edges in creation order -> rows (finite_differences_grid.cpp:38-154, nlp_functions.cpp:70-132, edge_set.cpp:31-42)
     struct E { int kind, k, dim, scale; };
     std::vector<E> lsq, eq, ineq;
+    const bool eq_lin = d.stage_eq == CORBO_HIP_STAGE_EQ_LINEAR, eq_user = stage_eq_is_user(d);
+    const int eq_rows = eq_user ? user_stage_rows(d.stage_eq) : 0;
     for (int k = 0; k < N - 1; ++k) {
         const int terms = CORBO_HIP_COST_TERMS(d.stage_cost);   // nlp_functions.cpp:70-107: state term, control term, dt term twice
         // (cost_nonlsq: plain objective edges are no rows of the LM residual -- getLsqObjectiveDimension() == 0; the LM entries refuse such a handle)
@@ -234,12 +265,13 @@ std::string build_structure(const corbo_hip_problem_desc& d, Structure& S)
         if (d.stage_ineq_control) ineq.push_back({EK_U_INEQ, k, 1, 2});   // the control term's edge on u_k (nlp_functions.cpp:82-89)
         if (d.stage_ineq_state_control) ineq.push_back({EK_XU_INEQ, k, user_stage_rows(d.stage_ineq_state_control), 2});   // the state-control term's edge on (x_k, u_k) (nlp_functions.cpp:109-115)
         if (d.ctrl_dev) ineq.push_back({EK_CTRL_DEV, k, nu, 2});
-        if (d.stage_eq && d.constraint_integration == 2) eq.push_back({EK_XI_EQ_LEFT, k, 1, 1});
-        eq.push_back({EK_DEFECT, k, (d.stage_eq && d.constraint_integration == 1) ? nx + 1 : nx, 1});
+        if (eq_lin && d.constraint_integration == 2) eq.push_back({EK_XI_EQ_LEFT, k, 1, 1});
+        if (eq_user) eq.push_back({EK_XU_EQ, k, eq_rows, 1});   // a user equality's state-control term on (x_k, u_k), in front of the dynamics edge (finite_differences_grid.cpp:58-61, 102-108)
+        eq.push_back({EK_DEFECT, k, (eq_lin && d.constraint_integration == 1) ? nx + 1 : nx, 1});
         if (d.stage_ineq != CORBO_HIP_INEQ_NONE && d.stage_ineq_integral) ineq.push_back({EK_XI_INEQ, k, 1, 2});
     }
-    S.eq_stride     = nx + (d.stage_eq ? 1 : 0);
-    S.eq_defect_off = (d.stage_eq && d.constraint_integration == 2) ? 1 : 0;
+    S.eq_stride     = nx + (eq_user ? eq_rows : eq_lin ? 1 : 0);
+    S.eq_defect_off = eq_user ? eq_rows : (eq_lin && d.constraint_integration == 2) ? 1 : 0;
     // TerminalEqualityConstraint: nx rows; TerminalPartialEqualityConstraint: one row per active component (final_state_constraints.h:219)
     const uint32_t feq_mask = d.final_eq_mask ? d.final_eq_mask : ((1u << nx) - 1u);
     int feq_dim = 0;
@@ -289,7 +321,7 @@ std::string build_structure(const corbo_hip_problem_desc& d, Structure& S)
                 v[2] = {S.off_dt, 1}; return 3;
             case EK_XI_EQ_LEFT: v[0] = {k * s, nx}; v[1] = {k * s + nx, nu}; v[2] = {S.off_dt, 1}; return 3;
             case EK_U_INEQ: v[0] = {k * s + nx, nu}; return 1;
-            case EK_XU_INEQ: v[0] = {k * s, nx}; v[1] = {k * s + nx, nu}; return 2;
+            case EK_XU_INEQ: case EK_XU_EQ: v[0] = {k * s, nx}; v[1] = {k * s + nx, nu}; return 2;
             case EK_CTRL_DEV:   // (u_k, u_prev, dt_prev): finite_differences_grid.cpp:51-53; the last one on (u_ref, u_{N-2}, dt), :149
                 if (k == N) { v[0] = {-2, nu}; v[1] = {(N - 2) * s + nx, nu}; v[2] = {S.off_dt, 1}; return 3; }
                 v[0] = {k * s + nx, nu};
@@ -320,7 +352,7 @@ std::string build_structure(const corbo_hip_problem_desc& d, Structure& S)
     };
     auto add_list = [&](const std::vector<E>& list) {
         for (const E& e : list) {
-            if (e.kind == EK_XI_INEQ || e.kind == EK_XI_EQ_LEFT || e.kind == EK_CTRL_DEV || e.kind == EK_U_INEQ || e.kind == EK_XU_INEQ) { add_extra(e); continue; }
+            if (e.kind == EK_XI_INEQ || e.kind == EK_XI_EQ_LEFT || e.kind == EK_CTRL_DEV || e.kind == EK_U_INEQ || e.kind == EK_XU_INEQ || e.kind == EK_XU_EQ) { add_extra(e); continue; }
             if (e.kind == EK_DEFECT && e.dim > nx) {   // TrapezoidalIntegralEqualityDynamicsEdge: the appended row as an XEdge over the dynamics edge's blocks
                 XEdge x{};
                 XV v[4];

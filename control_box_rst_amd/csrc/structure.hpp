@@ -51,7 +51,8 @@ enum EdgeKind : int32_t {
     EK_XI_EQ_ROW  = 19,     // the integral row the trapezoidal rule appends to the dynamics edge (TrapezoidalIntegralEqualityDynamicsEdge: dimension nx + 1)
     EK_CTRL_DEV   = 20,     // TernaryVectorScalarVertexEdge<computeNonIntegralControlDeviationTerm> (u_k, u_prev, dt_prev)
     EK_U_INEQ     = 21,     // UnaryVectorVertexEdge<computeNonIntegralControlTerm> on u_k: a user stage inequality's control term (csrc/stage_functions/)
-    EK_XU_INEQ    = 22      // BinaryVectorVertexEdge<computeNonIntegralStateControlTerm> on (x_k, u_k): its state-control term, 1 to 4 rows (nlp_functions.cpp:109-115)
+    EK_XU_INEQ    = 22,     // BinaryVectorVertexEdge<computeNonIntegralStateControlTerm> on (x_k, u_k): its state-control term, 1 to 4 rows (nlp_functions.cpp:109-115)
+    EK_XU_EQ      = 23      // the same edge of a user stage EQUALITY (nlp_functions.cpp:142-145), added in front of the interval's dynamics edge: 1 to 4 rows, scale 1
 };
 
 // One "extra" edge (the kinds above), evaluated by a lane of the sweep kernel's generic loop (sweep_body, XE): attached vertices with their storage
@@ -105,8 +106,8 @@ struct Structure {
     std::vector<int32_t> jac_rows, jac_cols;  // structure in value order
     std::vector<int32_t> param_voff;     // parameter -> vertex storage offset
     std::vector<XEdge> xedges;           // integral-form constraint edges / control-deviation edges (empty for every other descriptor)
-    int eq_stride = 0;                   // residual rows per interval in the equality section (nx; nx + 1 with an integral equality row)
-    int eq_defect_off = 0;               // row of the dynamics defect inside the interval's equality rows (1 behind a LeftSumEqualityEdge)
+    int eq_stride = 0;                   // residual rows per interval in the equality section (nx; nx + 1 with an integral equality row; nx + rows with a user state-control equality)
+    int eq_defect_off = 0;               // row of the dynamics defect inside the interval's equality rows (1 behind a LeftSumEqualityEdge, rows behind a user state-control equality)
     // big-block family with non-diagonal weights (corbo_hip_create_weighted; desc.weights_dense holds the mask): the factors as the kernels read them,
     // [Q | R | Qf] in blocks of wdense_stride(nx) = nx * nx doubles (R row-major with stride nu in the first nu * nu of its block); empty otherwise
     std::vector<double> wside;
@@ -155,8 +156,10 @@ bool build_bt_tables(const Structure& S, const std::vector<int32_t>& jmap, int n
 
 // returns "" on success, otherwise an error text
 std::string validate_desc(const corbo_hip_problem_desc& d);
-// rows of a registered state-control stage function (csrc/stage_functions/, kind 2), 1 for the functions of the other kinds, -1 = no such id
+// rows of a registered state-control stage function (csrc/stage_functions/, kind 2 / 3), 1 for the functions of the other kinds, -1 = no such id
 int user_stage_rows(int id);
+// desc.stage_eq names a user state-control equality (CORBO_HIP_STAGE_FN_USER + slot), not the linear integral row (CORBO_HIP_STAGE_EQ_LINEAR)
+inline bool stage_eq_is_user(const corbo_hip_problem_desc& d) { return d.stage_eq >= CORBO_HIP_STAGE_FN_USER; }
 std::string build_structure(const corbo_hip_problem_desc& d, Structure& out);
 // corbo_hip_create_weighted: the factors beside the descriptor (checked before any HIP call).  nx <= 4: the descriptor path's structure (factors moved
 // into q_sqrt / r_sqrt / qf_sqrt, weights_dense = mask); big-block family: Structure::wside

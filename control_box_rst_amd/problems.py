@@ -128,6 +128,17 @@ def with_state_control_ineq(d: ProblemDesc, slot: int, params) -> ProblemDesc:
     return d
 
 
+def with_state_control_eq(d: ProblemDesc, slot: int, params) -> ProblemDesc:
+    """Add the stage equalities' non-integral state-control term e(x_k, u_k) = 0 -- the user function registered in `slot` of csrc/stage_functions/
+    (kind=state_control_eq; shipped: 4 = heading_tie, 6 = input_circle) -- to a descriptor: `stage_eq` names it, its up to eight parameters are
+    `stage_eq_params[0..7]` (they travel inside the descriptor)."""
+    prm = [float(v) for v in params] + [0.0] * 8
+    d.stage_eq = capi.STAGE_FN_USER + int(slot)
+    for i in range(len(d.stage_eq_params)):
+        d.stage_eq_params[i] = prm[i] if i < 8 else 0.0
+    return d
+
+
 def min_time_quadratic(d: ProblemDesc, q, r, only_last_n=0) -> ProblemDesc:
     """Turn a time-optimal descriptor (free dt, MinimumTime) into the reference's MinTimeQuadratic(Q, R, integral=False, lsq=True)
     (hybrid_cost.h:189-303): the quadratic form's state and control terms next to the minimum-time term; only_last_n > 0: on the

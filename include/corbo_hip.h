@@ -116,9 +116,13 @@ typedef enum corbo_hip_stage_ineq {
  * subclass (stage_functions.h:276-310).  kind = state_ineq: its non-integral STATE term c(x_k) (dimension 1), named in `stage_ineq`, parameters
  * `ineq_params`; kind = control_ineq: its non-integral CONTROL term c(u_k) (dimension 1), named in `stage_ineq_control`, parameters `ineq_control_params`;
  * kind = state_control_ineq: its non-integral STATE-CONTROL term c(x_k, u_k) (1 to 4 rows, `value<NX, NU>(x, u, prm, out)`), named in
- * `stage_ineq_state_control`, parameters through corbo_hip_set_state_control_params.
+ * `stage_ineq_state_control`, parameters through corbo_hip_set_state_control_params; kind = state_control_eq: the non-integral STATE-CONTROL term
+ * e(x_k, u_k) = 0 of a user's corbo::StageEqualityConstraint subclass (1 to 4 rows, the same `value<NX, NU>(x, u, prm, out)`), named in `stage_eq`, parameters
+ * `stage_eq_params[0 .. 7]`.
  * Shipped examples: slot 0 = tilt cone x[6]^2 + x[7]^2 - alpha^2 (state), slot 1 = input magnitude |u|^2 - r^2 (control), slot 2 = drive power
- * (u[0] x[2])^2 - P^2 (state-control, 1 row), slot 3 = input envelope |u_i| <= a_i + b_i x[2]^2, i = 0, 1 (state-control, 4 rows). */
+ * (u[0] x[2])^2 - P^2 (state-control, 1 row), slot 3 = input envelope |u_i| <= a_i + b_i x[2]^2, i = 0, 1 (state-control, 4 rows), slot 4 = heading tie
+ * u[1] - p0 u[0] x[2] - p1 = 0 (state-control equality, 1 row), slot 6 = input circle u[0]^2 + u[1]^2 - p0 - p1 x[2]^2 = 0, u[2] - p2 x[0] u[0] - p3 = 0
+ * (state-control equality, 2 rows). */
 #define CORBO_HIP_STAGE_FN_USER 1000
 
 typedef enum corbo_hip_final_ineq {
@@ -218,6 +222,12 @@ typedef struct corbo_hip_problem_desc {
      * stage_eq: corbo_hip_stage_eq, the stage equalities' integral state-control term e(x, u) (one row).  TrapezoidalRule: the row is APPENDED to the
      *   interval's dynamics edge (TrapezoidalIntegralEqualityDynamicsEdge, :149-216: dimension nx + 1); LeftSum: a LeftSumEqualityEdge on (x_k, u_k, dt)
      *   in front of the dynamics edge (:368-410).
+     *   OR (the two uses exclude each other) CORBO_HIP_STAGE_FN_USER + slot of a registered `state_control_eq` function: the stage equalities' NON-INTEGRAL
+     *   state-control term e(x_k, u_k) = 0 (getNonIntegralStateControlTermDimension = 1 .. 4) -- one BinaryVectorVertexEdge on (x_k, u_k) per interval with the
+     *   function's rows, added in front of the interval's dynamics edge by every grid (nlp_functions.cpp:109-115, 142-145; finite_differences_grid.cpp:58-61;
+     *   multiple_shooting_grid.cpp:65-68).  Needs no constraint_integration; every grid; same limits as the other extra edges: Levenberg-Marquardt path,
+     *   3 <= N <= 1024, shooting integrators up to Runge-Kutta 4, no non-diagonal weights for nx > 4.  The function's eight parameters are
+     *   stage_eq_params[0 .. 7]: they travel inside the descriptor (the array is larger than eight doubles), no setter beside it.
      * ctrl_dev: corbo_hip_ctrl_dev, the stage inequalities' control-deviation term (getNonIntegralControlDeviationTermDimension = nu): one
      *   TernaryVectorScalarVertexEdge per interval on (u_k, u_{k-1}, dt) -- k = 0: on (u_0, the previously applied control, its age), both fixed,
      *   corbo_hip_set_previous_control -- and one behind the final-stage edges on (u_ref = 0, u_{N-2}, dt) (nlp_functions.cpp:117-131, 152-186,
@@ -227,7 +237,7 @@ typedef struct corbo_hip_problem_desc {
     int32_t stage_ineq_integral;
     int32_t stage_eq;
     int32_t ctrl_dev;
-    double stage_eq_params[CORBO_HIP_MAX_NX + CORBO_HIP_MAX_NU + 1];   /* CORBO_HIP_STAGE_EQ_LINEAR: a_1 .. a_nx, b_1 .. b_nu, c */
+    double stage_eq_params[CORBO_HIP_MAX_NX + CORBO_HIP_MAX_NU + 1];   /* CORBO_HIP_STAGE_EQ_LINEAR: a_1 .. a_nx, b_1 .. b_nu, c; a user state_control_eq function: its prm[0 .. 7] */
     double ctrl_dev_params[CORBO_HIP_MAX_NU];                          /* CORBO_HIP_CTRL_DEV_RATE: r_max per control */
     /* The stage inequalities' non-integral CONTROL term (getNonIntegralControlTermDimension = 1): 0 = none, else CORBO_HIP_STAGE_FN_USER + slot of a
      * registered `control_ineq` function -- one UnaryVectorVertexEdge on u_k per interval, created behind the state term's edge and in front of the
@@ -246,6 +256,7 @@ typedef struct corbo_hip_problem_desc {
 typedef enum corbo_hip_stage_eq {
     CORBO_HIP_STAGE_EQ_NONE   = 0,
     CORBO_HIP_STAGE_EQ_LINEAR = 1   /* e(x, u) = a^T x + b^T u - c (summed left to right: the x terms, then the u terms, then - c) */
+    /* CORBO_HIP_STAGE_FN_USER + slot: a registered `state_control_eq` function (non-integral term on (x_k, u_k), 1 to 4 rows) */
 } corbo_hip_stage_eq;
 typedef enum corbo_hip_ctrl_dev {
     CORBO_HIP_CTRL_DEV_NONE = 0,
@@ -331,7 +342,7 @@ int corbo_hip_create(const corbo_hip_problem_desc* desc, int batch, int device, 
 /* The same with an explicit choice of the factorisation ROUTE where a descriptor has two (A/B measurements and the cross-route parity tests;
  * the library reads no environment variable).  `route` = OR of:
  *   CORBO_HIP_ROUTE_FREE_DT_BAND  a free dt around a big-block model through the general band factorisation instead of the stage / chain kernels' border column
- *   CORBO_HIP_ROUTE_XE_BAND       extra edges (control-deviation term, integral-form constraint edges, a user control / state-control inequality) of the small-block families
+ *   CORBO_HIP_ROUTE_XE_BAND       extra edges (control-deviation term, integral-form constraint edges, a user control / state-control inequality, a user state-control equality) of the small-block families
  *                                 up to 256 grid points through the general band factorisation instead of the block-tridiagonal route (one launch per solve)
  * 0 = what corbo_hip_create chooses.  A flag that does not apply to the descriptor is ignored. */
 #define CORBO_HIP_ROUTE_FREE_DT_BAND 1u
@@ -651,13 +662,13 @@ int corbo_hip_set_profiling(corbo_hip_handle h, int enable);
  * descriptor names (the adapter's recogniser matches user systems against the library's plug-in models with it). */
 int corbo_hip_eval_dynamics(const corbo_hip_problem_desc* desc, int n, const double* x, const double* u, double* f);
 
-/* User stage functions (csrc/stage_functions/): kind of a registered id -- 0 state inequality, 1 control inequality, 2 state-control inequality, -1 = not
- * registered -- and the value c(v, prm) of a function of kind 0 / 1 (or of CORBO_HIP_INEQ_BALL) at n points, evaluated on the HOST by the very template the kernels compile: v [n][dim], out [n].
+/* User stage functions (csrc/stage_functions/): kind of a registered id -- 0 state inequality, 1 control inequality, 2 state-control inequality, 3 state-control
+ * equality, -1 = not registered -- and the value c(v, prm) of a function of kind 0 / 1 (or of CORBO_HIP_INEQ_BALL) at n points, evaluated on the HOST by the very template the kernels compile: v [n][dim], out [n].
  * Lets a caller check that a stage-function object it holds is the function an id names (the adapter's recogniser matches a graph's inequality edges with it,
  * like corbo_hip_eval_dynamics for a dynamics object).  Needs no GPU. */
 int corbo_hip_stage_function_kind(int id);
 int corbo_hip_eval_stage_function(int id, int dim, int n, const double* v, const double* prm, double* out);
-/* A registered state-control function (kind 2) on the host, through the header the kernels compile: x [n][nx], u [n][nu], prm [8] -> out [n][rows].
+/* A registered state-control function (kind 2, or a state-control equality, kind 3) on the host, through the header the kernels compile: x [n][nx], u [n][nu], prm [8] -> out [n][rows].
  * corbo_hip_stage_function_rows: its row count (1 .. 4); 1 for a function of the other kinds, -1 = no such id.
  * CORBO_HIP_ERR_INVALID: not such a function, nx / nu below its nx_min / nu_min.  Needs no GPU. */
 int corbo_hip_eval_stage_function_xu(int id, int nx, int nu, int n, const double* x, const double* u, const double* prm, double* out);
