@@ -261,7 +261,7 @@ struct corbo_hip_solver {
     int plain_kernel = 1;          // corbo_hip_set_option("plain_kernel"): 0 = the general fused pass kernel also where the plain instantiation applies (A/B, tests)
     bool second_rows = false;      // some component carries a second cost row (terminal equality, duplicated dt edge): never the plain instantiation
     int pass_threads = 0;          // corbo_hip_set_option("pass_threads"): 0 = the default workgroup size of the run-to-completion kernel
-    int lag_priority = 1;          // corbo_hip_set_option("lag_priority")
+    int lag_priority = 1;          // corbo_hip_set_option("lag_priority"): 0 = off, 1 = on except for launches that overlap a launch in flight on the other lane, 2 = on for every launch (A/B)
     bool phase_cycles = false;     // corbo_hip_set_option("phase_cycles"): per-instance phase totals (FactorParams::phase_cycles)
     long long* d_phase = nullptr;  // [batch][8]
     bool raw_stamps = false;       // corbo_hip_set_option("raw_stamps"): the per-pass stamp log as raw offsets (development builds)
@@ -1150,12 +1150,14 @@ static int solve_impl(corbo_hip_handle h, const corbo_hip_lm_opts* o, int new_ru
     // Lanes: an enqueued re-arming solve behind a solve that is still in flight takes the OTHER lane and does not wait for it (it starts from d_x0, not
     // from that solve's result), unless the launch would be in queue mode or a diagnostic that owns per-handle buffers is on.  Every other enqueued solve
     // continues from the newest iterate: it stays on the current lane, ordered behind both.  (A synchronous solve has drained both lanes already.)
+    bool overlaps_other_lane = false;   // this launch starts while the other lane's is in flight
     if (async) {
         const bool other_lane = rearm && h->async_lanes == 2 && h->async_pending > 0 && !(h->active > 4 * h->num_cus) && !h->profile && !h->phase_cycles &&
                                 h->pass_timeline_inst < 0 && !h->sweep_timeline && !h->d_work && !h->d_xe0;
         if (other_lane) {
             if (!h->lane_b_ready) { const int rc_l = create_second_lane(h); if (rc_l) return rc_l; }
             swap_lanes(h);
+            overlaps_other_lane = true;
             h->idle_busy = true;   // (the lane just left holds the solve in flight; this lane's earlier launches are ahead on its own stream)
         }
         else { const int rc_j = join_lanes(h); if (rc_j) return rc_j; }
@@ -1257,7 +1259,10 @@ static int solve_impl(corbo_hip_handle h, const corbo_hip_lm_opts* o, int new_ru
             fp.loop_passes = MAX_PASSES;
             fp.stagger = h->stagger;
             fp.pass_threads = h->pass_threads;
-            if (h->lag_priority && !(count_of[i] > 4 * h->num_cus)) fp.cu_table = h->d_queue + 16;
+            // the per-CU progress rows (lag-based issue priority, lm_pass_kernel) shorten the tail of a launch that has the chip to itself; under two lanes the next
+            // launch fills the tail's free slots anyway and the per-pass bookkeeping is pure cost (docs/measurements/r14.md: 0.3238 -> 0.3180 ms per headline step)
+            const bool lag_on = h->lag_priority == 2 || (h->lag_priority == 1 && !overlaps_other_lane);
+            if (lag_on && !(count_of[i] > 4 * h->num_cus)) fp.cu_table = h->d_queue + 16;
             if (h->result_sink) { fp.x_host = h->h_stage; fp.st_host = h->h_state; }
             if (count_of[i] > 4 * h->num_cus) {   // more instances than resident workgroups: instance queue
                 HIP_TRY(hipMemsetAsync(h->d_queue, 0, sizeof(int32_t), st_of[i]));

@@ -684,7 +684,8 @@ int corbo_hip_stage_function_rows(int id);
  *   "solve_timing"      0: corbo_hip_solve records no HIP timing events around its launches (corbo_hip_stats::solve_ms and corbo_hip_get_timing stay 0):
  *                       7 - 13 us less per call, what a caller that solves ONE problem per call wants (the drop-in adapter sets it)
  *   "ff_converged"      0: compute the outer iterations that follow a converged step instead of counting them (A/B and tests)
- *   "lag_priority"      0: no lag-based issue priority in the run-to-completion kernel
+ *   "lag_priority"      0: no lag-based issue priority in the run-to-completion kernel; 1 (default): on, except for an enqueued solve that
+ *                       overlaps the solve in flight on the handle's other lane (the next launch fills the tail, the bookkeeping only costs); 2: always on (A/B)
  *   "phase_cycles"      1: per-instance phase totals of the run-to-completion kernel (corbo_hip_get_phase_cycles)
  *   "plain_kernel"      1 (default): a run-to-completion solve of the plain problem class at the headline horizon -- N = 100, two-wave shape, fixed dt, diagonal
  *                       weights; no stage / final inequality, terminal equality, per-vertex references, instance queue or diagnostic option -- launches the
